@@ -3,13 +3,17 @@
 256x256 BEV rasters -- BASELINE.json configs[1]: 256x256x4 raster, DriveSceneGen default U-Net
 (train.py:39-57 with 4 in/out channels), 50-step DDIM, batch 16 per GPU, fp32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one denoising step of the whole batch: dsg_unet_forward + dsg_ddim_step through the C ABI,
 inputs already resident in HBM.  Samples are independent, so ranks shard them with NO data-path
 collective (weak scaling: 16 samples per GPU); the only communication is the timing barrier / max.
-Rank 0 prints ONE JSON line, with
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the headline figure
+and `ms_per_step`.  --dump-outputs DIR writes what the last timed step returned (rank 0's eps and x_prev) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+--full adds everything else the benchmark measures: the training / other-precision / other-size records, the
+data-parallel training record whenever a process group exists, and in the line
   roofline     -- the dominant kernel (3x3 stride-1 implicit-GEMM conv, fp32-equivalent as an fp16x2 split on the f16
                   matrix cores): algorithmic FLOPs of its launches / their summed duration, from HIP events
                   recorded on the launch stream inside the timed region (dsg_prof_*), against 2500 / 3 = 833 TF/s
@@ -70,9 +74,11 @@ def gpu_leg(args, rank, world):
     if args.separate_gn_stats:
         _lib.check(lib.dsg_set_tuning(5, 0))
 
+    last = {}   # the last step's model output, for --dump-outputs
+
     def step(i, x):
         t = ts[i % len(ts)]
-        eps = net(x, t).sample
+        eps = last["eps"] = net(x, t).sample
         return sch.step(eps, t, x).prev_sample
 
     def barrier():
@@ -130,7 +136,23 @@ def gpu_leg(args, rank, world):
         if args.prof_dump and rank == 0:
             _lib.check(lib.dsg_prof_dump(args.prof_dump.encode()))
         lib.dsg_prof_enable(0)
-    return dt, prof, per_rank, clock.spread()
+    return dt, prof, per_rank, clock.spread(), {"eps": last["eps"], "x_prev": x}
+
+
+DUMP_BYTES = 60 * 10 ** 6   # all --dump-outputs arrays together (npy headers aside)
+
+
+def dump_outputs(folder, arrays):
+    """Each array as folder/<name>.npy in float32.  One larger than its share of DUMP_BYTES is cut to a fixed, seeded
+    sample of its flattened elements (sorted indices, the same for every run at the same shape)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    share = DUMP_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.ravel()[np.unique(np.random.default_rng(14555).integers(0, a.size, share))]
+        np.save(os.path.join(folder, name + ".npy"), a)
 
 
 def cpu_leg(args):
@@ -872,9 +894,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=16, help="samples per GPU (BASELINE configs[1]: 16)")
     ap.add_argument("--ddim-steps", type=int, default=50)
-    ap.add_argument("--no-prof", action="store_true", help="disable the HIP-event roofline leg")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--prof-dump", default=None, help="write the per-launch HIP-event records (CSV) here")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: HIP-event roofline, CPU baseline, extra records, train_ddp, "
+                         "the full record (--full-record and --prof-dump imply it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (rank 0's eps and x_prev, float32) as DIR/<name>.npy")
+    ap.add_argument("--no-prof", action="store_true", help="disable the HIP-event roofline leg (with --full)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (with --full)")
+    ap.add_argument("--prof-dump", default=None, help="write the per-launch HIP-event records (CSV) here (implies --full)")
     ap.add_argument("--pure-f32", action="store_true",
                     help="disable the fp16x2-split conv path: every contraction on the f32 MFMA (A/B reference)")
     ap.add_argument("--separate-gn-stats", action="store_true",
@@ -883,8 +910,9 @@ def main():
                     help="threads for the CPU oracle (16 is the fastest setting on the 2x64-core GPU box: "
                          "32/64/128/256 threads run 1.1x/2x/4.4x/36x slower)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra records (mixed-precision forward, training step, small-batch sampling)")
-    ap.add_argument("--no-ddp", action="store_true", help="skip the data-parallel training record that runs whenever a process group exists")
+                    help="skip the extra records (mixed-precision forward, training step, small-batch sampling) (with --full)")
+    ap.add_argument("--no-ddp", action="store_true",
+                    help="skip the data-parallel training record that runs whenever a process group exists (with --full)")
     ap.add_argument("--ddp-fp32-batch", type=int, default=64, help="train_ddp: BASELINE configs[2], 64 per GPU (0: skip)")
     ap.add_argument("--ddp-bf16-batch", type=int, default=128, help="train_ddp: BASELINE configs[4], 128 per GPU (0: skip)")
     ap.add_argument("--ddp-steps", type=int, default=3)
@@ -896,6 +924,9 @@ def main():
     ap.add_argument("--full-record", default=None,
                     help="where the FULL record (every class row of every leg) is written; default gpurun_out/bench_full.json")
     args = ap.parse_args()
+    args.full = args.full or bool(args.full_record or args.prof_dump)
+    if not args.full:   # a plain run: the headline's steps and nothing else
+        args.no_prof = args.no_cpu = args.no_extras = args.no_ddp = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # asked for N GPUs without a launcher: start one rank per GPU ourselves (the same command line the driver uses)
@@ -925,7 +956,10 @@ def main():
     if args.gpus != world and rank == 0 and world > 1:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
 
-    dt, prof, per_rank, spread = gpu_leg(args, rank, world)
+    dt, prof, per_rank, spread, outputs = gpu_leg(args, rank, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    del outputs
     train_ddp = None
     if torch.distributed.is_initialized() and not args.no_ddp:
         # N > 1 (or the forced one-rank RCCL group): the data-parallel TRAINING step on every rank -- what north_star names
@@ -986,13 +1020,17 @@ def main():
                             alg_flops_per_launch=dom["flops_per_launch"],
                             time_share=dom["total_ms"] * 1e-3 / dt)
         flops_img = 352.98e9  # SURVEY 8d, cfg2 forward
+        # which contraction the convs ran: the profiled classes when the HIP-event leg ran, else the switches that turn the
+        # fp16x2 split off (--pure-f32, DSG_TUNING key 2 = 0)
+        split = ("conv3x3_s1_mfma_f16x2split" in prof) if prof else not (
+            args.pure_f32 or "2=0" in os.environ.get("DSG_TUNING", "").split(","))
         out = {
             "metric": "denoising-steps/sec (U-Net fwd) on 256x256 BEV rasters", "value": value,
             "unit": "image-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "step_ms_spread": spread, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f32 (3x3 and 1x1 convs: fp32-equivalent contraction as an fp16x2 split on the f16 MFMA, fp32 "
-                     "accumulate; everything else f32)" if "conv3x3_s1_mfma_f16x2split" in prof else "f32",
+                     "accumulate; everything else f32)" if split else "f32",
             "data": "synthetic",
             "config": {"workload": "BASELINE configs[1]: 256x256x4 BEV raster, DriveSceneGen default U-Net "
                                    "(56,575,748 params), 50-step DDIM (eta=0), batch 16 per GPU, fp32",
@@ -1032,9 +1070,11 @@ def main():
         out["summary"] = summary_of(out)
         # the FULL record (every class row of every leg, ~25 KB) goes to a file and to stderr; stdout's last line is the
         # compact line the driver parses (round 4's 25.6-KB line was not parsed: BENCH_r04.json "parsed": null)
-        full_path = write_full_record(out, args.full_record)
-        sys.stderr.write(json.dumps(out) + "\n")
-        sys.stderr.flush()
+        full_path = None
+        if args.full:
+            full_path = write_full_record(out, args.full_record)
+            sys.stderr.write(json.dumps(out) + "\n")
+            sys.stderr.flush()
         print(compact_line(out, full_path), flush=True)
     if torch.distributed.is_initialized():
         torch.distributed.barrier()

@@ -5,6 +5,10 @@ import importlib.util
 import json
 import os
 import re
+import subprocess
+import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -115,3 +119,46 @@ def test_round6_record_digests_the_end_to_end_loop_and_the_ddp_step():
     ddp = line["summary"]["train_ddp_fp32"]
     assert ddp["world"] == 8 and ddp["exposed_comm_ms"] == {"overlap": 3.0, "deferred": 8.0} and ddp["selfcheck_bitwise"] is True
     assert "per_rank_ms" not in ddp and line["summary"]["train_ddp_bf16"]["error"].startswith("RuntimeError")
+
+
+def test_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_the_same_way(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; an array beyond its share of the byte budget becomes a seeded sample of its elements,
+    the same indices on every run, so that two builds' dumps compare element for element."""
+    import numpy as np
+    import torch
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_BYTES", 2 * 4 * 1000)
+    small = torch.arange(600, dtype=torch.float64).reshape(2, 3, 100)
+    big = torch.linspace(-1, 1, 5000).reshape(5, 1000)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3, 100) and np.array_equal(s, small.numpy().astype(np.float32))
+    g = np.load(tmp_path / "a" / "big.npy")
+    assert g.dtype == np.float32 and g.ndim == 1 and 900 <= g.size <= 1000
+    assert np.array_equal(g, np.load(tmp_path / "b" / "big.npy"))
+    assert np.all(np.diff(g) > 0) and np.all(np.isin(g, big.numpy().ravel()))   # sorted indices of the flat array
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` as every measurement runs it: the headline keys, `ms_per_step` consistent with the
+    value over exactly K steps, none of --full's records, and --dump-outputs' files: the last timed step's eps and x_prev."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] is not None, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "image-steps/s" and line["higher_is_better"] is True
+    assert abs(line["value"] - 16 * 3 / (line["ms_per_step"] * 3e-3)) <= 1e-6 * line["value"]
+    assert "fp16x2 split" in line["dtype"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["full_record"] is None and not line["summary"]
+    for name in ("eps", "x_prev"):
+        a = np.load(out / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (16, 4, 256, 256) and np.isfinite(a).all(), name
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 * 10 ** 6

@@ -197,7 +197,7 @@ def test_train_ddp_record_on_a_one_rank_rccl_group():
     TRAINING step through Accelerator + GradBuckets on RCCL, timed with the buckets off / overlapped / deferred, with the
     bitwise self-check of the two modes -- so the first multi-GPU run measures the exchange north_star names.  Here: the
     forced one-rank RCCL communicator (an average over one rank is the identity; every collective is still issued)."""
-    out = _launcher(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras", "--no-prof",
+    out = _launcher(["bench.py", "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras", "--no-prof",
                      "--ddp-fp32-batch", "4", "--ddp-bf16-batch", "4", "--ddp-steps", "2"], force=True)
     rec, summ = _ddp_record(out)
     for name in ("train_ddp_fp32", "train_ddp_bf16"):
@@ -212,7 +212,7 @@ def test_train_ddp_record_on_a_one_rank_rccl_group():
 def test_train_ddp_record_of_two_ranks_sharing_the_gpu():
     """World 2 on the box's one GPU over gloo: the all-reduce really mixes two different shards' gradients (rank-specific
     samples), both modes still give the same slab bit for bit on both ranks, the global rate counts both ranks."""
-    out = _launcher(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras", "--no-prof",
+    out = _launcher(["bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras", "--no-prof",
                      "--ddp-fp32-batch", "2", "--ddp-bf16-batch", "0", "--ddp-steps", "2"], force=False,
                     extra_env={"DSG_DIST_BACKEND": "gloo"}, nproc=2)
     rec, summ = _ddp_record(out)
