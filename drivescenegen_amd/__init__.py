@@ -5,8 +5,8 @@ pipeline/training_pipeline.py} import from diffusers: same names, arguments, sta
 checkpoint folder; all arithmetic runs in hand-written HIP kernels behind the C ABI of include/dsg.h.
 """
 from .unet import UNet2DModel  # noqa: F401
-from .schedulers import DDPMScheduler, DDIMScheduler  # noqa: F401
-from .pipelines import DDPMPipeline, DDIMPipeline, ImagePipelineOutput  # noqa: F401
+from .schedulers import DDPMScheduler, DDIMScheduler, RePaintScheduler  # noqa: F401
+from .pipelines import DDPMPipeline, DDIMPipeline, RePaintPipeline, ImagePipelineOutput  # noqa: F401
 from .optimization import get_cosine_schedule_with_warmup  # noqa: F401
 from .train_loop import fit, notebook_launcher, sample_to_pil  # noqa: F401
 from .training import AdamW, Accelerator, GradBuckets, clip_grad_norm_, mse_loss  # noqa: F401

@@ -78,6 +78,20 @@ class ConvWgradArgs(C.Structure):
     ]
 
 
+class RepaintStepArgs(C.Structure):
+    """Mirror of ``dsg_repaint_step_args`` (include/dsg.h)."""
+    _fields_ = [
+        ("sample", C.c_void_p), ("eps", C.c_void_p), ("original", C.c_void_p), ("mask", C.c_void_p), ("noise", C.c_void_p),
+        ("prev", C.c_void_p), ("noise_out", C.c_void_p),
+        ("n", C.c_int32), ("c", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("original_n", C.c_int32), ("mask_n", C.c_int32), ("mask_c", C.c_int32),
+        ("add_std", C.c_int32),
+        ("sqrt_beta_prod_t", C.c_float), ("sqrt_alpha_prod_t", C.c_float), ("clip", C.c_float),
+        ("sqrt_alpha_prev", C.c_float), ("dir_coef", C.c_float), ("std", C.c_float), ("sqrt_beta_prev", C.c_float),
+        ("seed", C.c_uint64), ("offset", C.c_uint64),
+    ]
+
+
 class UNetConfig(C.Structure):
     """Mirror of ``dsg_unet_config`` (include/dsg.h)."""
     _fields_ = [
@@ -166,6 +180,8 @@ SIGNATURES = {
     "dsg_add_noise_philox": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, C.c_uint64, C.c_uint64, _vp],
     "dsg_ddpm_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
     "dsg_ddim_step": [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp],
+    "dsg_repaint_step": [C.POINTER(RepaintStepArgs), _vp],
+    "dsg_repaint_undo": [_vp, _vp, _vp, _i64, _f32, _f32, C.c_uint64, C.c_uint64, _vp],
     "dsg_postprocess": [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "dsg_unet_create": [C.POINTER(UNetConfig), C.POINTER(_vp)],
     "dsg_unet_set_param": [_vp, C.c_char_p, _vp, _i64, _vp],

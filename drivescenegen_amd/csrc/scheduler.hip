@@ -160,6 +160,123 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// RePaint (Lugmayr et al., CVPR 2022, Algorithm 1; diffusers' RePaintScheduler.step / .undo_step): scene completion with an
+// unconditional network.  One pass per reverse step, per element and in THIS order (include/dsg.h states it as the contract):
+//   p0      = (x - sb*e) / sa, clamped to +-clip when clip > 0                 (pred_x0 above)
+//   unknown = sap*p0 + dc*e     [+ std*z  when add_std]
+//   known   = sap*orig + sbp*z
+//   prev    = m*known + (1 - m)*unknown
+// z is ONE noise value per element, used in both places: read from `nz` (device memory or a pinned host buffer, SRC 0) or made
+// here from the Philox stream above (SRC 1: element e = lane e % 4 of block e / 4, dsg_philox_normal's mapping).  Each lane
+// owns one Philox block = 4 consecutive elements; with hw % 4 == 0 and 16-byte aligned pointers (VEC) those share (n, c), so
+// every stream is one dwordx4 access and `orig` / `m` are addressed through their batch / channel strides (0 = broadcast).
+struct repaint_geom {
+  int64_t numel, chw, hw;
+  int64_t orig_sn;          // 0 (one original for the batch) or chw
+  int64_t m_sn, m_sc;       // mask strides over n and c: 0 where its extent is 1
+};
+
+__device__ __forceinline__ float repaint_elem(float x, float e, float o, float m, float z, float sb, float sa, float clip,
+                                              float sap, float dc, float sd, float sbp, bool add_std) {
+  const float p0 = pred_x0(x, e, sb, sa, clip);
+  float unknown = __fadd_rn(__fmul_rn(sap, p0), __fmul_rn(dc, e));
+  if (add_std) unknown = __fadd_rn(unknown, __fmul_rn(sd, z));
+  // (the empty asm pins this product in a register of its own: hipcc otherwise pairs it with sbp*z into v_pk_mul_f32 and sums
+  //  the pair with v_pk_add_f32 ... op_sel:[0,1], the form tests/test_isa_policy.py bans; same arithmetic, same rounding)
+  float ko = __fmul_rn(sap, o);
+  asm volatile("" : "+v"(ko));
+  const float known = __fadd_rn(ko, __fmul_rn(sbp, z));
+  return __fadd_rn(__fmul_rn(m, known), __fmul_rn(__fsub_rn(1.0f, m), unknown));
+}
+
+template <int SRC>
+__device__ __forceinline__ void repaint_noise4(const float* nz, int64_t c, int64_t numel, bool vec, uint32_t seed_lo,
+                                               uint32_t seed_hi, uint32_t off_lo, uint32_t off_hi, float (&z)[4]) {
+  const int64_t e = c << 2;
+  if (SRC == 0) {
+    if (vec) {
+      const float4 v = *reinterpret_cast<const float4*>(nz + e);
+      z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
+    } else {
+      for (int k = 0; k < 4; ++k) z[k] = e + k < numel ? nz[e + k] : 0.f;
+    }
+  } else {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), off_lo, off_hi, seed_lo, seed_hi, r);
+    box_muller(r[0], r[1], z[0], z[1]);
+    box_muller(r[2], r[3], z[2], z[3]);
+  }
+}
+
+template <int SRC, bool VEC>
+__global__ __launch_bounds__(256) void repaint_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                           const float* __restrict__ orig, const float* __restrict__ mask,
+                                                           const float* __restrict__ nz, float* __restrict__ prev,
+                                                           float* __restrict__ noise_out, repaint_geom g, float sb, float sa,
+                                                           float clip, float sap, float dc, float sd, float sbp, int add_std,
+                                                           uint32_t seed_lo, uint32_t seed_hi, uint32_t off_lo,
+                                                           uint32_t off_hi) {
+  const int64_t blocks = (g.numel + 3) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const bool sdz = add_std != 0;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < blocks; c += stride) {
+    float z[4];
+    repaint_noise4<SRC>(nz, c, g.numel, VEC, seed_lo, seed_hi, off_lo, off_hi, z);
+    const int64_t e = c << 2;
+    if (VEC) {
+      const int64_t n = e / g.chw, rem = e - n * g.chw;
+      const int64_t ch = rem / g.hw, p = rem - ch * g.hw;
+      const float4 xv = *reinterpret_cast<const float4*>(x + e);
+      const float4 ev = *reinterpret_cast<const float4*>(eps + e);
+      const float4 ov = *reinterpret_cast<const float4*>(orig + n * g.orig_sn + rem);
+      const float4 mv = *reinterpret_cast<const float4*>(mask + n * g.m_sn + ch * g.m_sc + p);
+      float4 r;
+      r.x = repaint_elem(xv.x, ev.x, ov.x, mv.x, z[0], sb, sa, clip, sap, dc, sd, sbp, sdz);
+      r.y = repaint_elem(xv.y, ev.y, ov.y, mv.y, z[1], sb, sa, clip, sap, dc, sd, sbp, sdz);
+      r.z = repaint_elem(xv.z, ev.z, ov.z, mv.z, z[2], sb, sa, clip, sap, dc, sd, sbp, sdz);
+      r.w = repaint_elem(xv.w, ev.w, ov.w, mv.w, z[3], sb, sa, clip, sap, dc, sd, sbp, sdz);
+      *reinterpret_cast<float4*>(prev + e) = r;
+      if (noise_out) *reinterpret_cast<float4*>(noise_out + e) = make_float4(z[0], z[1], z[2], z[3]);
+    } else {
+      for (int k = 0; k < 4 && e + k < g.numel; ++k) {
+        const int64_t i = e + k;
+        const int64_t n = i / g.chw, rem = i - n * g.chw;
+        const int64_t ch = rem / g.hw, p = rem - ch * g.hw;
+        prev[i] = repaint_elem(x[i], eps[i], orig[n * g.orig_sn + rem], mask[n * g.m_sn + ch * g.m_sc + p], z[k], sb, sa,
+                               clip, sap, dc, sd, sbp, sdz);
+        if (noise_out) noise_out[i] = z[k];
+      }
+    }
+  }
+}
+
+// RePaint's jump back in time (one forward-diffusion step): out = ck*x + cz*z, z as above
+template <int SRC, bool VEC>
+__global__ __launch_bounds__(256) void repaint_undo_kernel(const float* __restrict__ x, const float* __restrict__ nz,
+                                                           float* __restrict__ out, int64_t numel, float ck, float cz,
+                                                           uint32_t seed_lo, uint32_t seed_hi, uint32_t off_lo,
+                                                           uint32_t off_hi) {
+  const int64_t blocks = (numel + 3) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < blocks; c += stride) {
+    float z[4];
+    repaint_noise4<SRC>(nz, c, numel, VEC, seed_lo, seed_hi, off_lo, off_hi, z);
+    const int64_t e = c << 2;
+    if (VEC) {
+      const float4 xv = *reinterpret_cast<const float4*>(x + e);
+      float4 r;
+      r.x = __fadd_rn(__fmul_rn(ck, xv.x), __fmul_rn(cz, z[0]));
+      r.y = __fadd_rn(__fmul_rn(ck, xv.y), __fmul_rn(cz, z[1]));
+      r.z = __fadd_rn(__fmul_rn(ck, xv.z), __fmul_rn(cz, z[2]));
+      r.w = __fadd_rn(__fmul_rn(ck, xv.w), __fmul_rn(cz, z[3]));
+      *reinterpret_cast<float4*>(out + e) = r;
+    } else {
+      for (int k = 0; k < 4 && e + k < numel; ++k) out[e + k] = __fadd_rn(__fmul_rn(ck, x[e + k]), __fmul_rn(cz, z[k]));
+    }
+  }
+}
+
 // (x/2 + 0.5).clamp(0,1), NCHW -> NHWC.  grid = (ceil(hw/256), n)
 template <int MODE>
 __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restrict__ x, void* __restrict__ out, int c,
@@ -269,6 +386,69 @@ DSG_API int dsg_add_noise_philox(const float* x0, const float* sqrt_a, const flo
   hipLaunchKernelGGL(dsg::philox_kernel<2>, dim3(dsg::philox_blocks(numel)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      x0, sqrt_a, sqrt_1ma, noisy, (void*)noise, numel, per_sample, (uint32_t)seed, (uint32_t)(seed >> 32),
                      (uint32_t)offset, (uint32_t)(offset >> 32));
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
+
+namespace dsg {
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+}  // namespace dsg
+
+DSG_API int dsg_repaint_step(const dsg_repaint_step_args* a, void* stream) {
+  DSG_CHECK_ARG(a, "dsg_repaint_step: NULL args");
+  DSG_CHECK_ARG(a->sample && a->eps && a->original && a->mask && a->prev, "dsg_repaint_step: NULL pointer");
+  DSG_CHECK_ARG(a->n > 0 && a->c > 0 && a->h > 0 && a->w > 0, "dsg_repaint_step: extents must be positive (n=%d c=%d h=%d w=%d)",
+                a->n, a->c, a->h, a->w);
+  DSG_CHECK_ARG(a->original_n == 1 || a->original_n == a->n,
+                "dsg_repaint_step: original_n=%d is neither 1 nor the batch %d", a->original_n, a->n);
+  DSG_CHECK_ARG(a->mask_n == 1 || a->mask_n == a->n, "dsg_repaint_step: mask_n=%d is neither 1 nor the batch %d", a->mask_n,
+                a->n);
+  DSG_CHECK_ARG(a->mask_c == 1 || a->mask_c == a->c, "dsg_repaint_step: mask_c=%d is neither 1 nor the channel count %d",
+                a->mask_c, a->c);
+  dsg::repaint_geom g;
+  g.hw = (int64_t)a->h * a->w;
+  g.chw = g.hw * a->c;
+  g.numel = g.chw * a->n;
+  g.orig_sn = a->original_n == 1 ? 0 : g.chw;
+  g.m_sc = a->mask_c == 1 ? 0 : g.hw;
+  g.m_sn = a->mask_n == 1 ? 0 : g.hw * a->mask_c;
+  const bool vec = (g.hw & 3) == 0 && dsg::aligned16(a->sample) && dsg::aligned16(a->eps) && dsg::aligned16(a->original) &&
+                   dsg::aligned16(a->mask) && dsg::aligned16(a->prev) && dsg::aligned16(a->noise) &&
+                   dsg::aligned16(a->noise_out);
+  const dim3 grid(dsg::philox_blocks(g.numel)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t s0 = (uint32_t)a->seed, s1 = (uint32_t)(a->seed >> 32), o0 = (uint32_t)a->offset, o1 = (uint32_t)(a->offset >> 32);
+#define DSG_REPAINT_LAUNCH(SRC, VEC)                                                                                          \
+  hipLaunchKernelGGL((dsg::repaint_step_kernel<SRC, VEC>), grid, block, 0, st, a->sample, a->eps, a->original, a->mask,       \
+                     a->noise, a->prev, a->noise_out, g, a->sqrt_beta_prod_t, a->sqrt_alpha_prod_t, a->clip,                  \
+                     a->sqrt_alpha_prev, a->dir_coef, a->std, a->sqrt_beta_prev, a->add_std, s0, s1, o0, o1)
+  if (a->noise) {
+    if (vec) DSG_REPAINT_LAUNCH(0, true); else DSG_REPAINT_LAUNCH(0, false);
+  } else {
+    if (vec) DSG_REPAINT_LAUNCH(1, true); else DSG_REPAINT_LAUNCH(1, false);
+  }
+#undef DSG_REPAINT_LAUNCH
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
+
+DSG_API int dsg_repaint_undo(const float* sample, const float* noise, float* out, int64_t numel, float ck, float cz,
+                             uint64_t seed, uint64_t offset, void* stream) {
+  DSG_CHECK_ARG(sample && out, "dsg_repaint_undo: NULL pointer");
+  DSG_CHECK_ARG(numel > 0, "dsg_repaint_undo: numel must be positive");
+  const bool vec = (numel & 3) == 0 && dsg::aligned16(sample) && dsg::aligned16(out) && dsg::aligned16(noise);
+  const dim3 grid(dsg::philox_blocks(numel)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const uint32_t s0 = (uint32_t)seed, s1 = (uint32_t)(seed >> 32), o0 = (uint32_t)offset, o1 = (uint32_t)(offset >> 32);
+#define DSG_UNDO_LAUNCH(SRC, VEC)                                                                                     \
+  hipLaunchKernelGGL((dsg::repaint_undo_kernel<SRC, VEC>), grid, block, 0, st, sample, noise, out, numel, ck, cz, s0, \
+                     s1, o0, o1)
+  if (noise) {
+    if (vec) DSG_UNDO_LAUNCH(0, true); else DSG_UNDO_LAUNCH(0, false);
+  } else {
+    if (vec) DSG_UNDO_LAUNCH(1, true); else DSG_UNDO_LAUNCH(1, false);
+  }
+#undef DSG_UNDO_LAUNCH
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }

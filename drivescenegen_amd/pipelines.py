@@ -1,4 +1,5 @@
-"""``DDPMPipeline`` / ``DDIMPipeline`` -- the sampler objects DriveSceneGen's scripts call.
+"""``DDPMPipeline`` / ``DDIMPipeline`` -- the sampler objects DriveSceneGen's scripts call -- and ``RePaintPipeline``, scene
+completion (keep part of a scene, generate the rest) with the same unconditional network.
 
 Reference call sites:
  - /root/reference/DriveSceneGen/pipeline/training_pipeline.py:101 ``DDPMPipeline(unet=..., scheduler=...)``,
@@ -22,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .schedulers import DDIMScheduler, DDPMScheduler, _randn_like_reference
+from .schedulers import DDIMScheduler, DDPMScheduler, RePaintScheduler, _randn_like_reference
 from .unet import UNet2DModel
 
 
@@ -78,7 +79,8 @@ class _PipelineBase:
         with open(os.path.join(path, "model_index.json")) as f:
             index = json.load(f)
         sched_name = index.get("scheduler", ["diffusers", "DDPMScheduler"])[1]
-        sched_cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler}.get(sched_name)
+        sched_cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
+                     "RePaintScheduler": RePaintScheduler}.get(sched_name)
         if sched_cls is None:
             raise NotImplementedError(f"scheduler class {sched_name!r} not supported")
         if cls._scheduler_cls is not sched_cls:
@@ -277,3 +279,157 @@ class DDIMPipeline(_PipelineBase):
             eps = self.unet(image, tdev[i]).sample
             image = self.scheduler.step(eps, t, image, eta=eta, generator=generator).prev_sample
         return self._finish(image, output_type, return_dict)
+
+
+def _is_pil(x):
+    try:
+        from PIL import Image
+    except ImportError:
+        return False
+    return isinstance(x, Image.Image)
+
+
+def _as_model_domain(image):
+    """`image` -> float32 host tensor [N, C, H, W] in the model's domain: float tensors / arrays are taken as they are
+    ([N, C, H, W] or [C, H, W]); PIL images and uint8 arrays ([.., H, W, C] or [H, W]) are mapped by x/255*2 - 1 (diffusers'
+    ``_preprocess_image`` without its resize)."""
+    if isinstance(image, (list, tuple)):
+        if not image:
+            raise ValueError("RePaintPipeline: empty image list")
+        return torch.cat([_as_model_domain(im) for im in image], dim=0)
+    if _is_pil(image):
+        image = np.array(image)
+        if image.dtype != np.uint8:
+            raise ValueError(f"RePaintPipeline: PIL image of mode with dtype {image.dtype} not supported (8-bit modes only)")
+    if isinstance(image, torch.Tensor):
+        if image.dtype == torch.uint8:
+            image = image.cpu().numpy()
+        else:
+            t = image.detach().to("cpu", torch.float32)
+            if t.dim() == 3:
+                t = t[None]
+            if t.dim() != 4:
+                raise ValueError(f"RePaintPipeline: image must be [N, C, H, W] (got shape {tuple(image.shape)})")
+            return t.contiguous()
+    arr = np.asarray(image)
+    if arr.dtype == np.uint8:
+        if arr.ndim == 2:
+            arr = arr[..., None]
+        if arr.ndim == 3:
+            arr = arr[None]
+        if arr.ndim != 4:
+            raise ValueError(f"RePaintPipeline: uint8 image must be [N, H, W, C] (got shape {arr.shape})")
+        arr = arr.transpose(0, 3, 1, 2).astype(np.float32) / np.float32(255.0) * np.float32(2.0) - np.float32(1.0)
+        return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
+    if not np.issubdtype(arr.dtype, np.floating):
+        raise ValueError(f"RePaintPipeline: image dtype {arr.dtype} not supported (float in the model's domain, or uint8)")
+    return _as_model_domain(torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)))
+
+
+def _as_binary_mask(mask):
+    """`mask` -> float32 host tensor [N, C, H, W] of 0 / 1 (< 0.5 -> 0, else 1; 1 keeps): float / bool tensors and arrays
+    [N, C, H, W], [C, H, W] or [H, W]; PIL "L" images and uint8 arrays are scaled by 1/255 first."""
+    if isinstance(mask, (list, tuple)):
+        if not mask:
+            raise ValueError("RePaintPipeline: empty mask list")
+        return torch.cat([_as_binary_mask(m) for m in mask], dim=0)
+    if _is_pil(mask):
+        mask = np.array(mask.convert("L"))
+    if isinstance(mask, torch.Tensor):
+        mask = mask.detach().cpu().numpy()
+    arr = np.asarray(mask)
+    if arr.dtype == np.uint8:
+        arr = arr.astype(np.float32) / np.float32(255.0)
+    elif arr.dtype == np.bool_ or np.issubdtype(arr.dtype, np.floating):
+        arr = arr.astype(np.float32)
+    else:
+        raise ValueError(f"RePaintPipeline: mask dtype {arr.dtype} not supported (float, bool or uint8)")
+    if arr.ndim == 2:
+        arr = arr[None, None]
+    elif arr.ndim == 3:
+        arr = arr[None]
+    if arr.ndim != 4:
+        raise ValueError(f"RePaintPipeline: mask_image must be [N, C, H, W] (got shape {arr.shape})")
+    return torch.from_numpy(np.ascontiguousarray((arr >= 0.5).astype(np.float32)))
+
+
+class RePaintPipeline(_PipelineBase):
+    """Scene completion (diffusers 0.20.0 ``RePaintPipeline``; Lugmayr et al., CVPR 2022): where ``mask_image`` is 1 the
+    result IS ``image``; where it is 0 the unconditional network generates content that agrees with the kept part.  The mask
+    may differ per channel (keep the lane planes of a raster, re-draw the agent plane).  Each entry of the jump schedule is
+    either a U-Net forward + ONE ``dsg_repaint_step``, or a ``dsg_repaint_undo`` (the jump back in time)."""
+
+    _class_name = "RePaintPipeline"
+    _scheduler_cls = RePaintScheduler
+
+    def _check_inputs(self, image, mask_image, batch_size):
+        c = self.unet.config
+        ss = c.sample_size
+        h, w = (ss, ss) if isinstance(ss, int) else ss
+        orig, mask = _as_model_domain(image), _as_binary_mask(mask_image)
+        if tuple(orig.shape[1:]) != (c.in_channels, h, w):
+            raise ValueError(f"RePaintPipeline: image has shape {tuple(orig.shape)}, the network takes "
+                             f"[N, {c.in_channels}, {h}, {w}]")
+        n = int(orig.shape[0])
+        if batch_size is not None:
+            if int(batch_size) < 1 or (n != 1 and n != int(batch_size)):
+                raise ValueError(f"RePaintPipeline: batch_size={batch_size} with {n} images (one image, or one per sample)")
+            n = int(batch_size)
+        if (int(mask.shape[0]) not in (1, n) or int(mask.shape[1]) not in (1, c.in_channels)
+                or tuple(mask.shape[2:]) != (h, w)):
+            raise ValueError(f"RePaintPipeline: mask_image has shape {tuple(mask.shape)}, expected "
+                             f"[{n} or 1, {c.in_channels} or 1, {h}, {w}]")
+        return orig, mask, (n, c.in_channels, h, w)
+
+    @torch.no_grad()
+    def __call__(self, image, mask_image, num_inference_steps: int = 250, eta: float = 0.0, jump_length: int = 10,
+                 jump_n_sample: int = 10, generator=None, output_type="pil", return_dict: bool = True, batch_size=None,
+                 noise: str = "host", seed=None):
+        """`batch_size=K` with one `image`: K different completions of one scene (the original and the mask are shared by the
+        batch through the kernel's broadcast; diffusers has no such argument).  ``noise="device", seed=S``: no host draw at
+        all -- x_T and every later draw are the Philox tensors (S, 0), (S, 1), ... (``RePaintScheduler.use_device_noise``:
+        the same distribution as the default, not the same values; `generator` is not touched)."""
+        if noise not in ("host", "device"):
+            raise ValueError(f"RePaintPipeline: noise={noise!r} (supported: 'host', 'device')")
+        if noise == "device" and seed is None:
+            raise ValueError("RePaintPipeline: noise='device' needs seed=<int>")
+        orig, mask, full = self._check_inputs(image, mask_image, batch_size)
+        if self.device.type != "cuda":
+            raise RuntimeError("RePaintPipeline runs on the MI355X HIP engine only: call .to('cuda') first")
+        sch = self.scheduler
+        with torch.cuda.device(self.device):
+            orig, mask = orig.to(self.device), mask.to(self.device)
+            sch.set_timesteps(num_inference_steps, jump_length, jump_n_sample)
+            sch.eta = float(eta)
+            ts = [int(t) for t in sch.timesteps]
+            ratio = sch.config.num_train_timesteps // sch.num_inference_steps
+            t_last = ts[0] + 1
+            plan = []                                  # True: U-Net + step, False: undo (diffusers' loop, decided up front)
+            for t in ts:
+                plan.append(t < t_last)
+                t_last = t
+            stream = None
+            try:
+                if noise == "device":
+                    sch.use_device_noise(seed)
+                    x = sch.device_randn(full, self.device)
+                    draw = None
+                else:
+                    sch.use_host_noise()
+                    stream = _NoiseStream(full, generator, self.device,
+                                          count=1 + sum(1 if fwd else ratio for fwd in plan))
+                    x, draw = stream.draw(), stream.draw
+                tdev = _device_timestep_rows(sch.timesteps, full[0], self.device)
+                t_last = ts[0] + 1
+                for i, t in enumerate(ts):
+                    if plan[i]:
+                        eps = self.unet(x, tdev[i]).sample
+                        x = sch.step(eps, t, x, orig, mask, variance_noise=draw() if draw else None).prev_sample
+                    else:
+                        x = sch.undo_step(x, t_last, variance_noise=draw)
+                    t_last = t
+            finally:
+                if stream is not None:
+                    stream.close()
+                sch.use_host_noise()
+        return self._finish(x, output_type, return_dict)

@@ -1,4 +1,5 @@
-"""``DDPMScheduler`` / ``DDIMScheduler`` with the diffusers-0.20.0 protocol DriveSceneGen uses.
+"""``DDPMScheduler`` / ``DDIMScheduler`` with the diffusers-0.20.0 protocol DriveSceneGen uses, and ``RePaintScheduler``
+(scene completion with the same unconditional network; diffusers 0.20.0 ships it next to the other two).
 
 Reference call sites: /root/reference/DriveSceneGen/scripts/train.py:65 (``DDPMScheduler()``, all defaults),
 training_pipeline.py:76 (``.num_train_timesteps`` as a direct attribute), training_pipeline.py:80 and
@@ -8,7 +9,8 @@ Formulas: SURVEY.md App. A.3 / A.3b.
 
 Host side (this file): the beta / alpha-bar tables, the integer timestep tables and the per-step fp32
 scalars, computed with the same fp32 operation order as the reference so they are bit-identical.
-Device side: the elementwise tensor math, in libdsg.so (dsg_add_noise / dsg_ddpm_step / dsg_ddim_step).
+Device side: the elementwise tensor math, in libdsg.so (dsg_add_noise / dsg_ddpm_step / dsg_ddim_step / dsg_repaint_step /
+dsg_repaint_undo).
 """
 from __future__ import annotations
 
@@ -78,7 +80,7 @@ class DDPMScheduler:
             raise TypeError(f"{self._class_name}: unexpected arguments {sorted(unknown)}")
         cfg.update(kwargs)
         for key in ("beta_schedule", "trained_betas", "prediction_type", "thresholding", "timestep_spacing"):
-            if cfg[key] != self._defaults[key]:
+            if key in cfg and cfg[key] != self._defaults[key]:
                 raise NotImplementedError(f"{self._class_name}: {key}={cfg[key]!r} is outside the DriveSceneGen "
                                           f"path (supported: {self._defaults[key]!r})")
         self._check_extra(cfg)
@@ -312,3 +314,205 @@ class DDIMScheduler(DDPMScheduler):
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev)
+
+
+def _broadcast_extents(name, t, full, free):
+    """`t` must be a 4-d tensor whose extents equal `full` except, on the axes listed in `free`, where 1 is allowed."""
+    if t.dim() != 4 or any(int(t.shape[i]) != full[i] and not (i in free and int(t.shape[i]) == 1) for i in range(4)):
+        allowed = "[" + ", ".join(f"{full[i]} or 1" if i in free else str(full[i]) for i in range(4)) + "]"
+        raise ValueError(f"RePaintScheduler.step: {name} has shape {tuple(t.shape)}, expected {allowed}")
+
+
+class RePaintScheduler(DDIMScheduler):
+    """diffusers-0.20.0 ``RePaintScheduler`` (Lugmayr et al., "RePaint: Inpainting using Denoising Diffusion Probabilistic
+    Models", CVPR 2022, Algorithm 1): the DDIM-form reverse step of an UNCONDITIONAL network with the known region replaced,
+    at every step, by the original noised to that step's level, and ``undo_step`` -- the jump back in time that lets the
+    generated part harmonise with the known part.  diffusers is not installed where this project builds and the reference
+    tree holds no RePaint code: the formulas in include/dsg.h (``dsg_repaint_step``) and the paper are the specification.
+
+    Host side: the jump schedule (``set_timesteps``) and the per-step fp32 scalars, the latter through
+    ``DDIMScheduler._step_scalars``.  Device side: ONE ``dsg_repaint_step`` per reverse step, one ``dsg_repaint_undo`` per
+    forward-diffusion pass.
+
+    Noise.  By default every draw comes from the caller's generator in diffusers' order and shapes (one tensor per ``step``,
+    ``num_train_timesteps // num_inference_steps`` per ``undo_step``; a CPU generator draws on the host), so a seeded call
+    is reproducible against diffusers.  ``use_device_noise(seed)`` is this package's extension (like
+    ``train_steps(noise="device")``): nothing is drawn on the host, draw k of the scheduler is the Philox tensor named
+    (seed, offset + k) and is generated inside the step kernel, and ``undo_step`` is ONE pass with the closed form of its
+    passes, ``ck = sqrt(prod(1 - beta_i))``, ``cz = sqrt(1 - prod(1 - beta_i))``: the same distribution as the host mode,
+    NOT the same values."""
+
+    _class_name = "RePaintScheduler"
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", eta=0.0,
+                     trained_betas=None, clip_sample=True)
+
+    def _check_extra(self, cfg):
+        pass
+
+    def __init__(self, **kwargs):
+        DDPMScheduler.__init__(self, **kwargs)
+        self.final_alpha_cumprod = torch.tensor(1.0)
+        self.eta = float(self.config.eta)       # (diffusers: the pipeline overwrites this attribute per call)
+        self._undo_cache = {}
+        self.noise_mode, self.noise_seed, self.noise_offset = "host", None, 0
+
+    # ---- noise source -----------------------------------------------------------------------------------------
+    def use_host_noise(self):
+        self.noise_mode, self.noise_seed, self.noise_offset = "host", None, 0
+
+    def use_device_noise(self, seed: int, offset: int = 0):
+        """Every later draw is the Philox4x32-10 / Box-Muller tensor (seed, offset), (seed, offset + 1), ... of
+        ``dsg_philox_normal`` (see the class docstring: same distribution as the host mode, not the same values)."""
+        if seed is None:
+            raise ValueError("RePaintScheduler: noise='device' needs an integer seed")
+        self.noise_mode, self.noise_seed, self.noise_offset = "device", int(seed) & (2 ** 64 - 1), int(offset)
+
+    def _next_offset(self):
+        k, self.noise_offset = self.noise_offset, self.noise_offset + 1
+        return k & (2 ** 64 - 1)
+
+    def device_randn(self, shape, device):
+        """One device-mode draw as a tensor of its own (the pipeline's x_T): ``dsg_philox_normal`` at the next offset."""
+        if self.noise_mode != "device":
+            raise RuntimeError("RePaintScheduler.device_randn: call use_device_noise(seed) first")
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+        with torch.cuda.device(out.device):
+            _lib.check(_lib.load().dsg_philox_normal(_lib.ptr(out), out.numel(), self.noise_seed, self._next_offset(),
+                                                    _lib.stream_ptr(out.device)))
+        return out
+
+    # ---- timestep table ---------------------------------------------------------------------------------------
+    def set_timesteps(self, num_inference_steps: int, jump_length: int = 10, jump_n_sample: int = 10, device=None):
+        n_train = self.config.num_train_timesteps
+        n = min(n_train, int(num_inference_steps))
+        if n < 1 or jump_length < 1 or jump_n_sample < 1:
+            raise ValueError("RePaintScheduler.set_timesteps: num_inference_steps, jump_length and jump_n_sample must be >= 1")
+        self.num_inference_steps = n
+        jumps = {j: jump_n_sample - 1 for j in range(0, n - jump_length, jump_length)}
+        ts, t = [], n
+        while t >= 1:
+            t -= 1
+            ts.append(t)
+            if jumps.get(t, 0) > 0:
+                jumps[t] -= 1
+                for _ in range(jump_length):
+                    t += 1
+                    ts.append(t)
+        ts = np.array(ts, dtype=np.int64) * (n_train // n)
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+
+    # ---- scalars ----------------------------------------------------------------------------------------------
+    def _step_scalars(self, t: int, eta: float = 0.0):
+        s = super()._step_scalars(t, eta)
+        prev_t = self.previous_timestep(t)
+        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+        s["sqrt_beta_prev"] = float((1 - a_prev) ** 0.5)
+        return s
+
+    def undo_scalars(self, t: int):
+        """[(ck, cz)] of ``undo_step(sample, t)``'s passes (host mode), and the closed form of all of them (device mode)."""
+        ratio = self.config.num_train_timesteps // self.num_inference_steps
+        key = (t, ratio)
+        hit = self._undo_cache.get(key)
+        if hit is None:
+            if t < 0 or t + ratio > self.config.num_train_timesteps:
+                raise ValueError(f"RePaintScheduler.undo_step: timestep {t} + {ratio} passes leaves the beta table")
+            betas = [self.betas[t + i] for i in range(ratio)]
+            passes = [(float((1 - b) ** 0.5), float(b ** 0.5)) for b in betas]
+            keep = float(np.prod([1.0 - float(b) for b in betas], dtype=np.float64))
+            fused = (float(np.float32(np.sqrt(keep))), float(np.float32(np.sqrt(1.0 - keep))))
+            hit = self._undo_cache[key] = (passes, fused)
+        return hit
+
+    # ---- reverse step -----------------------------------------------------------------------------------------
+    def step(self, model_output, timestep, sample, original_image, mask, generator=None, return_dict: bool = True,
+             variance_noise=None):
+        """x_{t-1} from x_t, the network's output, the known scene and the mask (1 keeps, 0 generates).
+        `original_image` is [N or 1, C, H, W], `mask` [N or 1, C or 1, H, W] (fp32, broadcast by the kernel).
+        `variance_noise` (this package's extension, as in ``DDPMScheduler.step``): the call's noise tensor, already drawn --
+        a device tensor or a ``HostNoise``; otherwise it is drawn here from `generator`, or named by (seed, offset) in
+        device-noise mode."""
+        if not sample.is_cuda:
+            raise RuntimeError("RePaintScheduler.step runs on the MI355X HIP engine only (got a CPU tensor)")
+        if sample.dim() != 4 or sample.dtype != torch.float32:
+            raise ValueError("RePaintScheduler.step: the sample must be an fp32 [N, C, H, W] tensor")
+        if tuple(model_output.shape) != tuple(sample.shape):
+            raise ValueError(f"RePaintScheduler.step: model output {tuple(model_output.shape)} != sample {tuple(sample.shape)}")
+        full = tuple(int(v) for v in sample.shape)
+        _broadcast_extents("original_image", original_image, full, (0,))
+        _broadcast_extents("mask", mask, full, (0, 1))
+        t = int(timestep)
+        s = self.step_scalars(t, self.eta)
+        x, e = sample.contiguous(), model_output.contiguous()
+        orig = original_image.to(x.device, torch.float32).contiguous()
+        m = mask.to(x.device, torch.float32).contiguous()
+        noise, host, nptr, seed, offset = None, None, None, 0, 0
+        if isinstance(variance_noise, HostNoise):
+            host = variance_noise
+            if tuple(host.shape) != full:
+                raise ValueError(f"variance_noise has shape {tuple(host.shape)}, the sample {full}")
+            nptr = host.device_ptr
+        elif variance_noise is not None:
+            noise = variance_noise.to(x.device, torch.float32).contiguous()
+            if tuple(noise.shape) != full:
+                raise ValueError(f"variance_noise has shape {tuple(noise.shape)}, the sample {full}")
+            nptr = _lib.ptr(noise)
+        elif self.noise_mode == "device":
+            seed, offset = self.noise_seed, self._next_offset()
+        else:
+            noise = _randn_like_reference(model_output.shape, generator, model_output.device, model_output.dtype).contiguous()
+            nptr = _lib.ptr(noise)
+        prev = torch.empty_like(x)
+        a = _lib.RepaintStepArgs(
+            sample=_lib.ptr(x), eps=_lib.ptr(e), original=_lib.ptr(orig), mask=_lib.ptr(m), noise=nptr, prev=_lib.ptr(prev),
+            noise_out=None, n=full[0], c=full[1], h=full[2], w=full[3], original_n=int(orig.shape[0]),
+            mask_n=int(m.shape[0]), mask_c=int(m.shape[1]), add_std=int(t > 0 and self.eta > 0),
+            sqrt_beta_prod_t=s["sqrt_beta_prod_t"], sqrt_alpha_prod_t=s["sqrt_alpha_prod_t"],
+            clip=1.0 if self.config.clip_sample else 0.0, sqrt_alpha_prev=s["sqrt_alpha_prev"], dir_coef=s["dir_coef"],
+            std=s["std"], sqrt_beta_prev=s["sqrt_beta_prev"], seed=seed, offset=offset)
+        import ctypes
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dsg_repaint_step(ctypes.byref(a), _lib.stream_ptr(x.device)))
+            if host is not None:
+                host.consumed = torch.cuda.Event()
+                host.consumed.record(torch.cuda.current_stream(x.device))
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)
+
+    def undo_step(self, sample, timestep, generator=None, variance_noise=None):
+        """Jump back: ``num_train_timesteps // num_inference_steps`` forward-diffusion passes from `timestep`, pass i with
+        ``beta = betas[timestep + i]`` and a fresh noise tensor (diffusers' indexing and order of draws).  In device-noise
+        mode: one pass with the closed form of all of them (class docstring).  `variance_noise`: the passes' noise tensors,
+        already drawn (a sequence of device tensors / ``HostNoise``), or a callable returning the next one."""
+        if not sample.is_cuda:
+            raise RuntimeError("RePaintScheduler.undo_step runs on the MI355X HIP engine only (got a CPU tensor)")
+        if sample.dtype != torch.float32:
+            raise ValueError("RePaintScheduler.undo_step: fp32 only")
+        passes, fused = self.undo_scalars(int(timestep))
+        x = sample.contiguous()
+        lib, st = _lib.load(), _lib.stream_ptr(x.device)
+        with torch.cuda.device(x.device):
+            if self.noise_mode == "device" and variance_noise is None:
+                out = torch.empty_like(x)
+                _lib.check(lib.dsg_repaint_undo(_lib.ptr(x), None, _lib.ptr(out), x.numel(), fused[0], fused[1],
+                                                self.noise_seed, self._next_offset(), st))
+                return out
+            for i, (ck, cz) in enumerate(passes):
+                if variance_noise is None:
+                    z = _randn_like_reference(x.shape, generator, x.device, x.dtype)
+                else:
+                    z = variance_noise() if callable(variance_noise) else variance_noise[i]
+                host = z if isinstance(z, HostNoise) else None
+                if tuple(z.shape) != tuple(x.shape):
+                    raise ValueError(f"undo_step: noise has shape {tuple(z.shape)}, the sample {tuple(x.shape)}")
+                if host is None:
+                    z = z.to(x.device, torch.float32).contiguous()
+                out = torch.empty_like(x)
+                _lib.check(lib.dsg_repaint_undo(_lib.ptr(x), host.device_ptr if host else _lib.ptr(z), _lib.ptr(out),
+                                                x.numel(), ck, cz, 0, 0, st))
+                if host is not None:
+                    host.consumed = torch.cuda.Event()
+                    host.consumed.record(torch.cuda.current_stream(x.device))
+                x = out
+        return x

@@ -375,6 +375,38 @@ int dsg_philox_normal(float* out, int64_t numel, uint64_t seed, uint64_t offset,
 int dsg_add_noise_philox(const float* x0, const float* sqrt_a /* device [N] */, const float* sqrt_1ma /* device [N] */,
                          float* noisy, float* noise, int32_t n, int64_t per_sample, uint64_t seed, uint64_t offset,
                          void* stream);
+/* RePaint (Lugmayr et al., CVPR 2022, Algorithm 1; diffusers 0.20.0 RePaintScheduler.step / .undo_step): keep the region of a
+ * scene that a mask marks and generate the rest with an UNCONDITIONAL network.  One pass over [n, c, h, w] per reverse step; per
+ * element, every operation rounded to fp32 on its own, in exactly this order (the contract tests/test_gpu_repaint.py pins):
+ *     p0      = (x - sqrt_beta_prod_t*e) / sqrt_alpha_prod_t          clamped to +-clip when clip > 0
+ *     unknown = sqrt_alpha_prev*p0 + dir_coef*e                       then  + std*z  when add_std != 0  (t > 0 and eta > 0)
+ *     known   = sqrt_alpha_prev*orig + sqrt_beta_prev*z
+ *     prev    = m*known + (1 - m)*unknown                             m: 1 keeps the original, 0 generates
+ * `original` is [original_n, c, h, w] and `mask` [mask_n, mask_c, h, w], dense, with original_n / mask_n in {1, n} and mask_c in
+ * {1, c}: an extent of 1 is broadcast by the kernel's addressing, nothing is materialised.  z is ONE value per element, used in
+ * both places.  Its source: `noise` != NULL -- [n, c, h, w] in device memory or device-accessible pinned host memory, read once
+ * (see dsg_ddpm_step); `noise` == NULL -- generated in the kernel, element e of the flat tensor = element e of
+ * dsg_philox_normal(numel, seed, offset), bit for bit.  `noise_out` (optional) receives the z that was used.  `prev` and
+ * `noise_out` must not overlap any input.  dsg_repaint_undo is RePaint's jump back (one forward-diffusion step):
+ * out = ck*x + cz*z with the same two noise sources.  Both: stream-asynchronous, no allocation, legal under stream capture;
+ * arguments are checked before any HIP call. */
+typedef struct {
+  const float* sample;      /* x_t        [n, c, h, w] */
+  const float* eps;         /* model out  [n, c, h, w] */
+  const float* original;    /* known scene [original_n, c, h, w] */
+  const float* mask;        /* [mask_n, mask_c, h, w] */
+  const float* noise;       /* [n, c, h, w], or NULL: Philox (seed, offset) */
+  float* prev;              /* x_{t-1}    [n, c, h, w] */
+  float* noise_out;         /* optional [n, c, h, w] */
+  int32_t n, c, h, w;
+  int32_t original_n, mask_n, mask_c;
+  int32_t add_std;
+  float sqrt_beta_prod_t, sqrt_alpha_prod_t, clip /* <=0: no clip */, sqrt_alpha_prev, dir_coef, std, sqrt_beta_prev;
+  uint64_t seed, offset;
+} dsg_repaint_step_args;
+int dsg_repaint_step(const dsg_repaint_step_args* args, void* stream);
+int dsg_repaint_undo(const float* sample, const float* noise /* NULL: Philox (seed, offset) */, float* out, int64_t numel,
+                     float ck, float cz, uint64_t seed, uint64_t offset, void* stream);
 /* Pipeline post-process (DDPMPipeline.__call__ tail, App. A.4): (x/2+0.5).clamp(0,1), NCHW -> NHWC;
  * mode 0: float out; mode 1: uint8 round (generation.py `.images`); mode 2: uint8 truncation
  * (training_pipeline.py:21-22). */
