@@ -220,6 +220,8 @@ SIGNATURES = {
     "dsg_prof_enable": [_i32],
     "dsg_set_tuning": [_i32, _i32],
     "dsg_tuning_epoch": [],
+    "dsg_get_tuning": [_i32, C.POINTER(_i32)],
+    "dsg_tuning_key": [C.c_char_p, C.POINTER(_i32)],
     "dsg_prof_dump": [C.c_char_p],
     "dsg_prof_summary": [_i32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)],
 }

@@ -10,6 +10,7 @@
 // Layout: qkv [N][3C][L] is the output of the fused q/k/v projection (a 1x1 conv over [N,C,L]);
 // channel = head*D + i, so a head's q/k/v are D rows of L contiguous floats.  out is [N][C][L].
 #include "dsg_h16.h"
+#include "tuning.h"
 
 namespace dsg {
 
@@ -393,14 +394,8 @@ __global__ __launch_bounds__(64 * ATM_NW, DSG_ATM_MINW) void attention_mfma8_ker
   }
 }
 
-static int g_att_mfma = 1;  // head_dim 8 on the matrix cores (tuning key 14: A/B against the VALU kernel)
-void attention_set_mfma(int v) { g_att_mfma = v; }
-static int g_att_bwd_split = 1;  // the fp32 tape's attention backward on the matrix cores, fp16x2 split (tuning key 38: A/B against the VALU kernels)
-void attention_set_bwd_split(int v) { g_att_bwd_split = v; }
-static int g_att_blocked = 1;  // the plan keeps q, k, v and the attention output channel-blocked (tuning key 25)
-void attention_set_blocked(int v) { g_att_blocked = v; }
 bool attention_blocked_ok(int c, int heads, int l) {
-  return g_att_mfma && g_att_blocked && heads > 0 && c % heads == 0 && c / heads == 8 && l % 32 == 0;
+  return g_tune.att_mfma && g_tune.att_blocked && heads > 0 && c % heads == 0 && c / heads == 8 && l % 32 == 0;
 }
 
 // exact: keep off the fp16x2-split matrix-core kernel (q, k, v beyond fp16's range: the plan's range guard)
@@ -410,7 +405,7 @@ static int launch_attention(const float* qkv, float* out, float* lse, int n, int
                             bool exact, int dt = DSG_F32) {
   // scores are kept in the log2 domain: q is pre-scaled by log2(e)/sqrt(D)
   const float qscale = 1.4426950408889634f / sqrtf((float)D);
-  if (D == 8 && g_att_mfma && !exact && l % 32 == 0) {
+  if (D == 8 && g_tune.att_mfma && !exact && l % 32 == 0) {
     const dim3 grid(cdiv(l, 32 * ATM_NW) * heads * n), block(64 * ATM_NW);
     if (dt == DSG_BF16) hipLaunchKernelGGL(attention_mfma8_kernel<1>, grid, block, 0, st, qkv, out, lse, c, heads, l, qscale);
     else if (dt == DSG_F16) hipLaunchKernelGGL(attention_mfma8_kernel<2>, grid, block, 0, st, qkv, out, lse, c, heads, l, qscale);
@@ -1093,7 +1088,7 @@ DSG_API int dsg_attention_bwd_dt(const float* qkv, const float* out, const float
   DSG_CHECK_ARG(qkv && out && dout && lse && dqkv && dsum_ws, "dsg_attention_bwd_dt: NULL pointer");
   DSG_CHECK_ARG(n > 0 && c > 0 && heads > 0 && l > 0 && c % heads == 0, "dsg_attention_bwd_dt: bad dims");
   DSG_CHECK_ARG(dtype >= DSG_F32 && dtype <= DSG_F16, "dsg_attention_bwd_dt: bad dtype %d", dtype);
-  if (dtype != DSG_F32 && c / heads == 8 && l % 32 == 0 && dsg::g_att_mfma)
+  if (dtype != DSG_F32 && c / heads == 8 && l % 32 == 0 && dsg::g_tune.att_mfma)
     return dtype == DSG_BF16
                ? dsg::launch_attention_bwd_mfma8<1>(qkv, out, dout, lse, dqkv, dsum_ws, n, c, heads, l, static_cast<hipStream_t>(stream))
                : dsg::launch_attention_bwd_mfma8<2>(qkv, out, dout, lse, dqkv, dsum_ws, n, c, heads, l, static_cast<hipStream_t>(stream));
@@ -1108,7 +1103,7 @@ DSG_API int dsg_attention_bwd(const float* qkv, const float* out, const float* d
   hipStream_t st = static_cast<hipStream_t>(stream);
   // head_dim 8 (every attention block of the reference's networks): the matrix-core kernels in their fp32-class form (PREC 0);
   // tuning key 14 = 0 keeps the VALU kernels for A/B
-  if (c / heads == 8 && l % 32 == 0 && dsg::g_att_mfma && dsg::g_att_bwd_split)
+  if (c / heads == 8 && l % 32 == 0 && dsg::g_tune.att_mfma && dsg::g_tune.att_bwd_split)
     return dsg::launch_attention_bwd_mfma8<0>(qkv, out, dout, lse, dqkv, dsum_ws, n, c, heads, l, st);
   switch (c / heads) {
     case 8: return dsg::launch_attention_bwd<8>(qkv, out, dout, lse, dqkv, dsum_ws, n, c, heads, l, st);

@@ -24,6 +24,7 @@
 // Epilogue: + bias (+ time-embedding column) (+ residual), 128-B row stores; optional 2x2 sum-pool
 // (the adjoint of the nearest-x2 upsample).
 #include "dsg_h16.h"
+#include "tuning.h"
 #include <cstdlib>
 #include <algorithm>
 
@@ -460,49 +461,13 @@ int conv_h2_stats_tiles(const dsg_conv_args* a, int hout, int wout);
 bool conv_in_eligible(const dsg_conv_args* a, int hout, int wout);
 int conv_in_stats_tiles(const dsg_conv_args* a, int hout, int wout);
 int conv_in_launch(const dsg_conv_args* a, int hout, int wout, hipStream_t st);
-void conv_in_set_enabled(int v);
 // conv_out.hip: normalised + activated channel-blocked activations -> fp32 [N,C<=8,H,W] image, every compute_dtype
 bool conv_out_eligible(const dsg_conv_args* a, int hout, int wout);
 int conv_out_launch(const dsg_conv_args* a, int hout, int wout, hipStream_t st);
-void conv_out_set_enabled(int v);
-void conv_h2_set_enabled(int on);
-void conv_h2_set_rows(int r);
-void conv_h2_set_stats(int on);
-void conv_h2_set_waves(int w);
-void conv_h2_set_pw_occ2(int v);
-void conv_h2_set_s2(int v);
-void conv_h2_set_bm32(int v);
-void conv_h2_set_bm32_small(int v);
-void conv_h2_set_bm128(int v);
-void conv_h2_set_splitk(int v);
-void conv_h2_set_ws2(int v);
-void conv_h2_set_fuse_sc(int v);
-int conv_h2_get_fuse_sc();
-void conv_h2_set_pre(int v);
-void conv_h2_set_narrow(int v);
-void conv_h2_set_splitk_mid(int v);
-void conv_h2_set_rows_rule(int v);
-void conv_h2_set_gnb(int v);
-void conv_h2_set_s2_nchw(int v);
-void conv_h2_set_gnb_bm64(int v);
-void attention_set_bwd_split(int v);
 bool conv_h2_gnb_ok(const dsg_conv_args* a, int hout, int wout);
-void conv_h2_set_pre_min_ct(int v);
 bool conv_h2_takes_operand(const dsg_conv_args* a, int hout, int wout, bool wanted);
-void attention_set_blocked(int v);
 bool conv_h2_sc_fusable(const dsg_conv_args* a, int hout, int wout);
 int conv_h2_splitk_slices(const dsg_conv_args* a, int hout, int wout, int* stat_splits);
-void unet_set_blocked(int v);
-void attention_set_mfma(int v);
-void wgrad_h2_set_enabled(int on);
-void conv_wgrad16_set_wide(int v);
-void conv_wgrad16_set_fold(int v);
-void wgrad_h2_set_wide(int v);
-void conv_wgrad16_set_pw(int v);
-void conv_h2_set_fold(int on);
-
-static int g_conv_fewout = 1;  // VALU kernel for cout <= 4 (tuning key 10: A/B against the zero-padded MFMA tile)
-static int g_conv_kc = 0;  // K-chunk of the 3x3 stride-1 kernel: 4 | 8 | 0 = by grid size (measured, r01)
 
 template <int KS, int STRIDE, int GM, int MT, int KC, int IO16 = 0>
 static int launch_mfma(const ConvP& p, hipStream_t st) {
@@ -812,7 +777,7 @@ int conv2d_fwd_impl(const dsg_conv_args* a, hipStream_t st, int force_direct) {
   const bool tile_ok = (p.wout % TW == 0 || narrow) && (p.hout % TH == 0) && (p.wstride % 32 == 0) && p.cin <= 2048 &&
                        (p.wstride >= ((p.cout + 31) / 32) * 32);
   const int s = a->stride, k = a->ksize, u = a->upsample;
-  if (!force_direct && g_conv_fewout && k == 3 && s == 1 && u == 0 && !p.pool && p.cout <= 4 && p.cin % FO_KC == 0 &&
+  if (!force_direct && g_tune.conv_fewout && k == 3 && s == 1 && u == 0 && !p.pool && p.cout <= 4 && p.cin % FO_KC == 0 &&
       (p.c1 == 0 || p.c0 % FO_KC == 0) && p.wout % TW == 0 && p.hout % FO_TH == 0)
     return launch_fewout(p, st);  // conv_out: too few output channels for the matrix cores
   if (io16 == 2 && !force_direct && tile_ok && k == 3 && s == 1 && u == 0 && !p.pool) {
@@ -847,7 +812,7 @@ int conv2d_fwd_impl(const dsg_conv_args* a, hipStream_t st, int force_direct) {
       // KC=4 keeps 3 workgroups per CU (30 KB LDS, 127 VGPRs): better when the grid has >= 3 per CU to give;
       // KC=8 (2 per CU, half the barriers) wins on the low-resolution levels.  Few channels: KC=4.
       const int nblk = p.tiles_x * p.tiles_y * p.n * ((p.cout + 63) / 64);
-      const bool kc4 = p.cin <= 4 || !dual_ok8 || g_conv_kc == 4 || (g_conv_kc == 0 && nblk >= 768);
+      const bool kc4 = p.cin <= 4 || !dual_ok8 || g_tune.conv_kc == 4 || (g_tune.conv_kc == 0 && nblk >= 768);
       if (kc4 && dual_ok4) {
         if (u == 0) return mt2 ? launch_mfma<3, 1, 0, 2, 4>(p, st) : launch_mfma<3, 1, 0, 1, 4>(p, st);
         if (u == 1) return mt2 ? launch_mfma<3, 1, 1, 2, 4>(p, st) : launch_mfma<3, 1, 1, 1, 4>(p, st);
@@ -873,165 +838,6 @@ int conv2d_fwd_impl(const dsg_conv_args* a, hipStream_t st, int force_direct) {
 }
 
 }  // namespace dsg
-
-namespace dsg { int conv_h2_tuning_epoch(); }
-static int g_tuning_epoch = 0;   // every accepted dsg_set_tuning call (whatever file owns the switch)
-DSG_API int32_t dsg_tuning_epoch(void) { return dsg::conv_h2_tuning_epoch() + g_tuning_epoch; }
-
-// Tuning / A-B switches (key 1: K-chunk of the fp32 3x3 kernel, 0 = auto | 4 | 8; key 2: fp16x2-split 3x3 kernel
-// on/off).  Not part of the reference surface.
-static int set_tuning_impl(int32_t key, int32_t value);
-DSG_API int dsg_set_tuning(int32_t key, int32_t value) {
-  const int rc = set_tuning_impl(key, value);
-  if (rc == DSG_OK) ++g_tuning_epoch;   // host-side caches keyed on dsg_tuning_epoch see EVERY accepted key
-  return rc;
-}
-static int set_tuning_impl(int32_t key, int32_t value) {
-  {  // a test / measurement hook: production processes keep the library's global state immutable
-    const char* t = getenv("DSG_TESTING");
-    if (t == nullptr || t[0] != '1')
-      return dsg::fail(DSG_ERR_INVALID_ARG, "dsg_set_tuning: kernel-selection switches are a test hook (set DSG_TESTING=1 in the "
-                                            "environment); per-plan choices are in dsg_unet_config.flags");
-  }
-  if (key == 1 && (value == 0 || value == 4 || value == 8)) {
-    dsg::g_conv_kc = value;
-    return DSG_OK;
-  }
-  if (key == 2 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_enabled(value);
-    return DSG_OK;
-  }
-  if (key == 3 && (value == 0 || value == 2 || value == 3 || value == 4)) {
-    dsg::conv_h2_set_rows(value);
-    return DSG_OK;
-  }
-  if (key == 10 && (value == 0 || value == 1)) {
-    dsg::g_conv_fewout = value;
-    return DSG_OK;
-  }
-  if (key == 8 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_fold(value);
-    return DSG_OK;
-  }
-  if (key == 7 && (value == 0 || value == 1)) {
-    dsg::wgrad_h2_set_enabled(value);
-    return DSG_OK;
-  }
-  if (key == 6 && (value == 4 || value == 8)) {
-    dsg::conv_h2_set_waves(value);
-    return DSG_OK;
-  }
-  if (key == 17 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_bm32_small(value);
-    return DSG_OK;
-  }
-  if (key == 19 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_splitk(value);
-    return DSG_OK;
-  }
-  if (key == 20 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_ws2(value);
-    return DSG_OK;
-  }
-  if (key == 25 && (value == 0 || value == 1)) {
-    dsg::attention_set_blocked(value);
-    dsg::conv_h2_set_fuse_sc(dsg::conv_h2_get_fuse_sc());  // (bumps the tuning epoch: the plan's arena changes)
-    return DSG_OK;
-  }
-  if (key == 23 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_fuse_sc(value);
-    return DSG_OK;
-  }
-  if (key == 26 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_pre(value);
-    return DSG_OK;
-  }
-  if (key == 34 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_splitk_mid(value);
-    return DSG_OK;
-  }
-  if (key == 32 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_narrow(value);
-    return DSG_OK;
-  }
-  if (key == 36 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_rows_rule(value);
-    return DSG_OK;
-  }
-  if (key == 37 && value >= 0 && value <= 3) {
-    dsg::conv_h2_set_gnb(value);
-    return DSG_OK;
-  }
-  if (key == 38 && (value == 0 || value == 1)) {
-    dsg::attention_set_bwd_split(value);
-    return DSG_OK;
-  }
-  if (key == 41 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_gnb_bm64(value);
-    return DSG_OK;
-  }
-  if (key == 40 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_s2_nchw(value);
-    return DSG_OK;
-  }
-  if (key == 39 && (value == 0 || value == 1)) {
-    dsg::conv_wgrad16_set_fold(value);
-    return DSG_OK;
-  }
-  if (key == 31 && (value == 0 || value == 1)) {
-    dsg::wgrad_h2_set_wide(value);
-    return DSG_OK;
-  }
-  if (key == 30 && (value == 0 || value == 1)) {
-    dsg::conv_wgrad16_set_pw(value);
-    return DSG_OK;
-  }
-  if (key == 29 && (value == 0 || value == 1)) {
-    dsg::conv_wgrad16_set_wide(value);
-    return DSG_OK;
-  }
-  if (key == 27 && value >= 1) {
-    dsg::conv_h2_set_pre_min_ct(value);
-    return DSG_OK;
-  }
-  if (key == 18 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_bm128(value);
-    return DSG_OK;
-  }
-  if (key == 16 && value >= 0) {
-    dsg::conv_h2_set_bm32(value);
-    return DSG_OK;
-  }
-  if (key == 15 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_s2(value);
-    return DSG_OK;
-  }
-  if (key == 14 && (value == 0 || value == 1)) {
-    dsg::attention_set_mfma(value);
-    return DSG_OK;
-  }
-  if (key == 13 && (value == 0 || value == 1)) {
-    dsg::unet_set_blocked(value);
-    return DSG_OK;
-  }
-  if (key == 11 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_pw_occ2(value);
-    return DSG_OK;
-  }
-  if (key == 22 && (value == 0 || value == 1)) {
-    dsg::conv_out_set_enabled(value);
-    return DSG_OK;
-  }
-  if (key == 21 && (value == 0 || value == 1)) {
-    dsg::conv_in_set_enabled(value);
-    return DSG_OK;
-  }
-  if (key == 5 && (value == 0 || value == 1)) {
-    dsg::conv_h2_set_stats(value);
-    return DSG_OK;
-  }
-  return dsg::fail(DSG_ERR_INVALID_ARG, "dsg_set_tuning: unknown key/value %d/%d", key, value);
-}
 
 DSG_API int dsg_conv2d_stats_tiles(const dsg_conv_args* a, int32_t* tiles) {
   DSG_CHECK_ARG(a != nullptr && tiles != nullptr, "dsg_conv2d_stats_tiles: NULL pointer");

@@ -18,6 +18,7 @@
 // LDS: dY tile [64 co][64 px (+1 pad)], patch [ci][rows*cols (odd stride)] -- both conflict-free for the
 // lane patterns of v_mfma_f32_32x32x2_f32 (A/B: 32 consecutive rows at a fixed k).
 #include "dsg_h16.h"
+#include "tuning.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -1096,15 +1097,11 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2w_kernel(WgradP p) {
   }
 }
 
-static int g_wgrad_h2_wide = 1;  // dsg_set_tuning key 31 (tests / A-B runs): 0 = the 32 x 64 workgroup everywhere
-void wgrad_h2_set_wide(int v) { g_wgrad_h2_wide = v; }
-static bool wgrad_h2_wide(int cout) { return g_wgrad_h2_wide && cout % WW_CO == 0; }
+static bool wgrad_h2_wide(int cout) { return g_tune.wgrad_h2_wide && cout % WW_CO == 0; }
 
-static int g_wgrad_h2 = 1;
-void wgrad_h2_set_enabled(int on) { g_wgrad_h2 = on; }
 
 static bool wgrad_h2_eligible(const WgradP& p, int ks, int stride, int ups) {
-  return g_wgrad_h2 && ks == 3 && stride == 1 && ups == 0 && p.cin % 32 == 0 && p.cout % 64 == 0 && p.wout % 32 == 0 &&
+  return g_tune.wgrad_h2 && ks == 3 && stride == 1 && ups == 0 && p.cin % 32 == 0 && p.cout % 64 == 0 && p.wout % 32 == 0 &&
          p.hout % 2 == 0 && (p.c1 == 0 || p.c0 % 32 == 0);
 }
 
@@ -1423,7 +1420,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_pw_kernel(WgradP p) {
 
 static bool wgrad_h2_pw_eligible(int cin, int c0, int c1, int cout, int ks, int stride, int ups, int plane) {
   (void)c0; (void)c1;
-  return g_wgrad_h2 && ks == 1 && stride == 1 && ups == 0 && cin % 64 == 0 && cout % 64 == 0 && plane % 64 == 0;
+  return g_tune.wgrad_h2 && ks == 1 && stride == 1 && ups == 0 && cin % 64 == 0 && cout % 64 == 0 && plane % 64 == 0;
 }
 
 // (tile, runs) of the pointwise split kernel: 128 x 128 tiles where both channel counts allow, about one workgroup per
@@ -2135,8 +2132,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad16_pw_kernel(Wgrad16PwP p) {
     }
 }
 
-static int g_wgrad16_pw = 1;  // dsg_set_tuning key 30 (tests / A-B runs): 0 = the 3x3 kernel's one-tap instantiation
-void conv_wgrad16_set_pw(int v) { g_wgrad16_pw = v; }
 // tile multiples of the pointwise kernel for these channel counts, and its runs per image (>= 512 workgroups where the map allows)
 static void wgrad16_pw_plan(int c0, int c1, int cout, int n, int plane, int* mi, int* nj, int* rpi) {
   const int cin = c0 + c1;
@@ -2148,17 +2143,13 @@ static void wgrad16_pw_plan(int c0, int c1, int cout, int n, int plane, int* mi,
   *rpi = r;
 }
 
-static int g_wgrad16_wide = 1;  // dsg_set_tuning key 29 (tests / A-B runs): 0 = the 64 x 64 workgroup everywhere
-void conv_wgrad16_set_wide(int v) { g_wgrad16_wide = v; }
-static int g_wgrad16_fold = 1;  // dsg_set_tuning key 39 (tests / A-B runs): 0 = Upsample2D's conv on the nine-tap kernel at full resolution
-void conv_wgrad16_set_fold(int v) { g_wgrad16_fold = v; }
 // Upsample2D's conv in the folded form (Wgrad16P.fold_co): the sampler form's shapes (wgrad16_ok) without GroupNorm in front
 static bool wgrad16_fold(const dsg_conv_wgrad_args* a) {
-  return g_wgrad16_fold && a->upsample == 1 && a->stride == 1 && a->ksize == 3 && a->c1 == 0 && a->gn_scale_shift == nullptr &&
+  return g_tune.wgrad16_fold && a->upsample == 1 && a->stride == 1 && a->ksize == 3 && a->c1 == 0 && a->gn_scale_shift == nullptr &&
          a->cout % 64 == 0 && a->win % 32 == 0 && a->hin % 2 == 0;
 }
 // co tiles per wave: 2 (a 64 ci x 128 co workgroup, one per CU) for the 3x3 gradients whose cout allows it
-static int wgrad16_cot(int cout, int ksize) { return (g_wgrad16_wide && ksize == 3 && cout % 128 == 0) ? 2 : 1; }
+static int wgrad16_cot(int cout, int ksize) { return (g_tune.wgrad16_wide && ksize == 3 && cout % 128 == 0) ? 2 : 1; }
 
 static void wgrad16_runs(int cin, int cout, int n, int hout, int wout, int cot, int* strips, int* rsplit, int* spw = nullptr) {
   const int pairs = (cin / 64) * (cout / (64 * cot));
@@ -2298,7 +2289,7 @@ static int launch_wgrad16_pw(const dsg_conv_wgrad_args* a, int plane, hipStream_
 }
 
 static int launch_wgrad16(const dsg_conv_wgrad_args* a, int hout, int wout, hipStream_t st) {
-  if (a->ksize == 1 && g_wgrad16_pw) return launch_wgrad16_pw(a, hout * wout, st);
+  if (a->ksize == 1 && g_tune.wgrad16_pw) return launch_wgrad16_pw(a, hout * wout, st);
   Wgrad16P p;
   const bool fold = wgrad16_fold(a);  // Upsample2D's conv: the K grid is x's own map, dY its space-to-depth image (Wgrad16P.fold_co)
   const int taps = fold ? 4 : a->ksize * a->ksize;

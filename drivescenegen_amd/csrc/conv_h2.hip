@@ -1,4 +1,4 @@
-// fp16x2-split / bf16 / fp16 matrix-core convolution: host side (eligibility, tuning switches, weight packing).
+// fp16x2-split / bf16 / fp16 matrix-core convolution: host side (eligibility, weight packing).
 // The kernel is conv_h2_kernel.h (see its header for the algorithm and the reference call sites); the launch logic is
 // conv_h2_launch.h, instantiated here for the fp32-equivalent split (PREC 0) and in conv_h2_bf16.hip /
 // conv_h2_f16.hip for the 16-bit modes (separate translation units: they compile in parallel).
@@ -6,16 +6,14 @@
 
 namespace dsg {
 
-H2Tuning g_h2;
-
 int conv_h2_launch_bf16(const dsg_conv_args* a, int hout, int wout, hipStream_t st);
 int conv_h2_launch_f16(const dsg_conv_args* a, int hout, int wout, hipStream_t st);
 
 // folded up-sampler mode: nearest x2 + 3x3 as four 2x2 convs of the low-resolution input (weight_h2_fold)
 bool conv_h2_fold(const dsg_conv_args* a) {
-  return g_h2.enabled && g_h2.fold && a->weight_h2_fold != nullptr && a->upsample == 1 && a->ksize == 3 && a->stride == 1 &&
+  return g_tune.enabled && g_tune.fold && a->weight_h2_fold != nullptr && a->upsample == 1 && a->ksize == 3 && a->stride == 1 &&
          !a->pool2 && !a->gn_scale_shift && !a->weight_h2_cout_stride && (a->c0 + a->c1) % 16 == 0 &&
-         (a->c1 == 0 || a->c0 % 16 == 0) && (a->win % H2_TW == 0 || (g_h2.narrow && (a->win == 16 || a->win == 8))) &&
+         (a->c1 == 0 || a->c0 % 16 == 0) && (a->win % H2_TW == 0 || (g_tune.narrow && (a->win == 16 || a->win == 8))) &&
          a->hin % 8 == 0 && a->cout % 8 == 0 &&
          (a->c0 + a->c1) <= 1024 && (a->compute_dtype == DSG_F32 || (a->src_layout == 1 && a->dst_layout == 1));
 }
@@ -24,11 +22,11 @@ bool conv_h2_fold(const dsg_conv_args* a) {
 bool conv_h2_s2(const dsg_conv_args* a, int hout, int wout) {
   // (also on fp32 [N,C,H,W] tensors, the fp32 tape's layout: its down-sampler convs and its up-samplers' data gradient, s2_window4)
   const bool lay_ok = (a->src_layout == 1 && a->dst_layout == 1) ||
-                      (a->src_layout == 0 && a->dst_layout == 0 && a->compute_dtype == DSG_F32 && (a->s2_window4 || g_h2.s2_nchw));
-  return g_h2.enabled && g_h2.s2 && a->weight_h2_s2 != nullptr && a->stride == 2 && a->ksize == 3 && !a->upsample &&
+                      (a->src_layout == 0 && a->dst_layout == 0 && a->compute_dtype == DSG_F32 && (a->s2_window4 || g_tune.s2_nchw));
+  return g_tune.enabled && g_tune.s2 && a->weight_h2_s2 != nullptr && a->stride == 2 && a->ksize == 3 && !a->upsample &&
          !a->pool2 && !a->gn_scale_shift && lay_ok && a->c1 == 0 && a->c0 % 8 == 0 &&
          a->cout % 8 == 0 && a->hin % 2 == 0 && a->win % 2 == 0 && hout % 8 == 0 &&
-         (wout % H2_TW == 0 || (g_h2.narrow && (wout == 16 || wout == 8)));
+         (wout % H2_TW == 0 || (g_tune.narrow && (wout == 16 || wout == 8)));
 }
 
 bool conv_h2_eligible(const dsg_conv_args* a, int hout, int wout) {
@@ -51,10 +49,10 @@ bool conv_h2_eligible(const dsg_conv_args* a, int hout, int wout) {
     return false;
   if (cin > 1024 && a->gn_scale_shift) return false;  // the GroupNorm scale/shift table shares LDS with the K-chunk buffers
   if (a->ksize == 1)  // pointwise: the map is re-tiled as (h*w/32) rows of 32 pixels, so only h*w matters
-    return g_h2.enabled && a->weight_h2 != nullptr && a->stride == 1 && !a->upsample && !a->pool2 && !a->temb &&
+    return g_tune.enabled && a->weight_h2 != nullptr && a->stride == 1 && !a->upsample && !a->pool2 && !a->temb &&
            cin % 16 == 0 && (a->c1 == 0 || a->c0 % 16 == 0) && (hout * wout) % (8 * H2_TW) == 0 && a->cout % 8 == 0;
   if (a->gn_scale_shift && (!a->silu || a->upsample)) return false;  // combinations the U-Net does not have
-  return g_h2.enabled && a->weight_h2 != nullptr && a->stride == 1 && a->upsample <= 1 && !a->pool2 &&
+  return g_tune.enabled && a->weight_h2 != nullptr && a->stride == 1 && a->upsample <= 1 && !a->pool2 &&
          cin % 16 == 0 && (a->c1 == 0 || a->c0 % 16 == 0) && (wout % H2_TW == 0 || wout == 16 || wout == 8) && (hout % 8 == 0) &&
          a->cout % 8 == 0;
 }
@@ -63,7 +61,7 @@ bool conv_h2_eligible(const dsg_conv_args* a, int hout, int wout) {
 // channel-blocked, no residual -- takes the 1x1 conv_shortcut over the resnet's raw input into its own K loop.
 // Every dsg_dtype; with split-K (small batches, fp32-equivalent mode) each K slice contracts its share of the shortcut too.
 bool conv_h2_sc_fusable(const dsg_conv_args* a, int hout, int wout) {
-  if (!g_h2.enabled || !g_h2.fuse_sc) return false;
+  if (!g_tune.enabled || !g_tune.fuse_sc) return false;
   if (a->ksize != 3 || a->stride != 1 || a->upsample || a->pool2 || !a->gn_scale_shift || !a->silu || a->residual) return false;
   if (a->src_layout != 1 || a->dst_layout != 1 || a->weight_h2 == nullptr) return false;
   if (a->weight_h2_cout_stride && a->weight_h2_cout_stride != (a->cout + 63) / 64 * 64) return false;  // (no column windows)
@@ -86,7 +84,7 @@ bool conv_h2_sc_fusable(const dsg_conv_args* a, int hout, int wout) {
 // adds the pays-off rule: the patch is staged by at least pre_min_ct workgroups (cout tiles x phases), i.e. the image
 // replaces that many normalise + activate + split passes over it.
 bool conv_h2_takes_operand(const dsg_conv_args* a, int hout, int wout, bool wanted) {
-  if (!g_h2.enabled || !g_h2.pre || a->compute_dtype != DSG_F32) return false;
+  if (!g_tune.enabled || !g_tune.pre || a->compute_dtype != DSG_F32) return false;
   if (a->ksize != 3 || a->stride != 1 || a->pool2 || a->src_layout != 1 || a->dst_layout != 1) return false;
   if (a->weight_h2_cout_stride) return false;
   const bool fold = conv_h2_fold(a);
@@ -96,8 +94,8 @@ bool conv_h2_takes_operand(const dsg_conv_args* a, int hout, int wout, bool want
   if ((fold ? a->win : wout) % H2_TW != 0 || !conv_h2_rows16(a, hout, wout)) return false;
   if (a->splitk_ws && conv_h2_splitk_slices(a, hout, wout, nullptr) > 1) return false;
   const int cin = a->c0 + a->c1;
-  if (g_h2.ws2 && !fold && cin <= 128) return false;  // (the two-workgroup kernel keeps its own staging)
-  if (wanted && ((a->cout + 63) / 64) * (fold ? 4 : 1) < g_h2.pre_min_ct) return false;
+  if (g_tune.ws2 && !fold && cin <= 128) return false;  // (the two-workgroup kernel keeps its own staging)
+  if (wanted && ((a->cout + 63) / 64) * (fold ? 4 : 1) < g_tune.pre_min_ct) return false;
   return true;
 }
 
@@ -110,14 +108,14 @@ bool conv_h2_takes_operand(const dsg_conv_args* a, int hout, int wout, bool want
 // prologue / epilogue: 62 (batch-5 sampling, per-launch records under the forced geometries, profiles/r05_geometry_sweep.txt:
 // the 256 -> 256 up-sampler conv at 5 x 640 tiles 148.3 us in 8-row tiles, 131.3 us in 16-row ones)
 static bool rows16_pays(int b16, int cost8 = 55) {
-  if (g_h2.rows == 2 || b16 <= 0) return false;
-  if (g_h2.rows == 4) return true;
+  if (g_tune.rows == 2 || b16 <= 0) return false;
+  if (g_tune.rows == 4) return true;
   // up to 128 tiles the 8-row grid still fits one round at 0.55 each.  129 .. 255 tiles go by the rounds rule as well: 160
   // workgroups of 16 rows on 62 % of the CUs beat 320 of 8 rows in two rounds (batch-5 sampling 6.03 -> 5.81 ms per step,
   // batch 3 4.05 -> 3.94, same-box A/B; the rule used to be "never below 256 tiles": key 3 = 3 keeps it for comparisons)
-  if (g_h2.rows == 3 ? b16 < 256 : b16 <= 128) return false;
+  if (g_tune.rows == 3 ? b16 < 256 : b16 <= 128) return false;
   const int r16 = (b16 + 255) / 256, r8 = (2 * b16 + 255) / 256;
-  return 100 * r16 <= (g_h2.rows_rule ? cost8 : 55) * r8;
+  return 100 * r16 <= (g_tune.rows_rule ? cost8 : 55) * r8;
 }
 
 bool conv_h2_rows16(const dsg_conv_args* a, int hout, int wout) {
@@ -134,7 +132,7 @@ bool conv_h2_rows16(const dsg_conv_args* a, int hout, int wout) {
   // Three-slice split-K (129 .. 170 eight-row tiles with long K: batch-5 sampling at the 32 x 32 level, generation.py:14-20):
   // 16-row tiles make that 3 x 65 .. 85 workgroups -- ONE round on 76-100 % of the chip, each workgroup with twice the MFMAs
   // per staged patch -- instead of two rounds of 8-row ones (per-launch records: 90.7 -> 84.2 us on the 512 -> 512 convs).
-  if (g_h2.rows_rule && g_h2.rows == 0 && b16 > 0 && a->splitk_ws != nullptr && a->ksize == 3 && a->stride == 1) {
+  if (g_tune.rows_rule && g_tune.rows == 0 && b16 > 0 && a->splitk_ws != nullptr && a->ksize == 3 && a->stride == 1) {
     int sp = 1;
     if (2 * b16 > H2_CUS / 2 && conv_h2_splitk_slices(a, hout, wout, &sp) == 3 && 3 * b16 <= H2_CUS) return true;
   }
@@ -146,7 +144,7 @@ bool conv_h2_rows16(const dsg_conv_args* a, int hout, int wout) {
 // (training_pipeline.py:26-32) at the 64 x 64 level: 64 x 4 slices of 64 couts against 128 x 2 of 32 -- the same 256 workgroups,
 // half the K chain, twice the MFMAs per staged patch (per-launch records, profiles/r05_geometry_sweep.txt: -5..-11 % on those convs).
 bool splitk_prefers_bm64(int grid64, int nq) {
-  if (!g_h2.rows_rule || !g_h2.splitk) return false;
+  if (!g_tune.rows_rule || !g_tune.splitk) return false;
   const int slices = std::min(4, std::min(H2_CUS / std::max(grid64, 1), nq / 4));
   // (long K only: a slice keeps at least six chunks -- with the 128 -> 128 convs' eight chunks cut in two the reduce pass costs
   //  more than the shorter chain saves: batch 1 measured +3.5 % without this condition)
@@ -157,7 +155,7 @@ bool splitk_prefers_bm64(int grid64, int nq) {
 // or pointwise; only when the tile grid the launcher would use covers at most half the CUs and K is long enough to cut.
 int conv_h2_splitk_slices(const dsg_conv_args* a, int hout, int wout, int* stat_splits) {
   if (stat_splits) *stat_splits = 1;
-  if (!g_h2.splitk || a->compute_dtype != DSG_F32 || a->src_layout != 1 || a->dst_layout != 1 || a->upsample) return 1;
+  if (!g_tune.splitk || a->compute_dtype != DSG_F32 || a->src_layout != 1 || a->dst_layout != 1 || a->upsample) return 1;
   if (!conv_h2_eligible(a, hout, wout)) return 1;
   const bool s2 = conv_h2_s2(a, hout, wout);
   int th = hout, tw = wout;
@@ -167,12 +165,12 @@ int conv_h2_splitk_slices(const dsg_conv_args* a, int hout, int wout, int* stat_
   }
   // maps narrower than a tile (16 x 16, 8 x 8: BASELINE configs[3]'s deepest levels -- 512 channels at 16 x 16 -- are ten
   // convs of a step on 64 workgroups at batch 8) split like the others: the slabs and the reduce pass are layout-only
-  const bool narrow_ok = g_h2.narrow && a->ksize == 3 && (tw == 16 || tw == 8);
+  const bool narrow_ok = g_tune.narrow && a->ksize == 3 && (tw == 16 || tw == 8);
   if ((tw % H2_TW != 0 && !narrow_ok) || th % 8 != 0) return 1;
   const int cout_pad = (a->cout + 63) / 64 * 64;
   int grid = ((tw + H2_TW - 1) / H2_TW) * (th / 8) * a->n * (cout_pad / H2_BM);
   const int nq = (s2 ? 4 * a->c0 : a->c0 + a->c1) / H2_KC;
-  if (a->ksize == 3 && !s2 && g_h2.bm32_small && grid <= H2_CUS / 2 && tw % H2_TW == 0 && !splitk_prefers_bm64(grid, nq))
+  if (a->ksize == 3 && !s2 && g_tune.bm32_small && grid <= H2_CUS / 2 && tw % H2_TW == 0 && !splitk_prefers_bm64(grid, nq))
     grid *= 2;  // (the launcher's 32-cout workgroups)
   if (nq < 8) return 1;
   int slices;
@@ -182,7 +180,7 @@ int conv_h2_splitk_slices(const dsg_conv_args* a, int hout, int wout, int* stat_
     // rounds of a third of the work: 0.67 of the time by the rounds model, measured -2.2 % on the batch-5 step (6.25 -> 6.11 ms,
     // interleaved same-box passes).  Four slices for 171 .. 192 workgroups (three rounds of a quarter, 0.75 by the model) measured
     // +1.4 % at batch 3 and +2.7 % at batch 6: not taken.  Long K only (24 chunks); key 34.
-    if (!g_h2.splitk_mid || nq < 24 || 3 * grid > 2 * H2_CUS) return 1;
+    if (!g_tune.splitk_mid || nq < 24 || 3 * grid > 2 * H2_CUS) return 1;
     slices = 3;
   } else {
     slices = std::min(4, std::min(H2_CUS / grid, nq / 4));
@@ -309,53 +307,53 @@ int splitk_reduce_launch(const float* part, int slices, const dsg_conv_args* a, 
 
 bool conv_h16_bm128(const dsg_conv_args* a, int hout, int wout, bool* r16) {
   const int cout_pad = (a->cout + 63) / 64 * 64;
-  if (!g_h2.bm128 || cout_pad % 128 != 0 || wout % H2_TW != 0) return false;
+  if (!g_tune.bm128 || cout_pad % 128 != 0 || wout % H2_TW != 0) return false;
   // GroupNorm-backward epilogue over cat(x0, x1) whose seam is not a multiple of 128 channels (the 64 + 64 concat of the outermost
   // up block): 64-cout workgroups, two per CU.  The 128-cout tile CAN read x across the seam (the epilogue picks the tensor per
   // 32-channel slab), but on these short-K convs its epilogue is not hidden behind anything: bf16 B=128 step 180.4 ms against
   // 179.8 with the statistics pass, and 178.2 against 178.8 on 64-cout workgroups (profiles/r06_gnb_seam_ab.txt)
-  if (a->gnb_x0 != nullptr && a->gnb_x1 != nullptr && a->gnb_c0 % 128 != 0 && g_h2.gnb_seam64) return false;
+  if (a->gnb_x0 != nullptr && a->gnb_x1 != nullptr && a->gnb_c0 % 128 != 0 && g_tune.gnb_seam64()) return false;
   // ... and so do ALL calls with the epilogue (key 41): one 128-cout workgroup per CU runs its VALU-bound epilogue with nothing beside
   // it, two 64-cout workgroups run it under each other's K loops -- bf16 B=128 step 175.7-175.9 ms against 177.3-177.5 with the
   // 128-cout workgroups (only the convs with at most 128 / 256 dY channels: 176.4-176.6 / 175.8-176.5; profiles/r06_gnb_bm64_ab.txt)
-  if (a->gnb_x0 != nullptr && g_h2.gnb_bm64) return false;
+  if (a->gnb_x0 != nullptr && g_tune.gnb_bm64) return false;
   const int per_row = (wout / H2_TW) * a->n * (cout_pad / 128);
   *r16 = hout % 16 == 0 && per_row * (hout / 16) >= H2_CUS;
   return per_row * (hout / (*r16 ? 16 : 8)) >= H2_CUS;
 }
 
 bool conv_h2_gnb_ok(const dsg_conv_args* a, int hout, int wout) {
-  if (!g_h2.enabled || !g_h2.gnb || !g_h2.stats || !conv_h2_eligible(a, hout, wout)) return false;
+  if (!g_tune.enabled || !g_tune.gnb_mode() || !g_tune.stats || !conv_h2_eligible(a, hout, wout)) return false;
   if (a->ksize != 3 || a->stride != 1 || a->upsample || a->pool2 || a->gn_scale_shift || a->sc_weight_h2 || a->src_operand ||
       a->residual || a->weight_h2 == nullptr || wout % H2_TW != 0 || hout % 8 != 0 || a->gnb_ss == nullptr)
     return false;
   const int lay = (a->src_layout ? 1 : 0) | (a->dst_layout ? 2 : 0);
   const bool h16 = a->compute_dtype != DSG_F32;
   if (h16 ? lay != 3 : lay != 0) return false;
-  if (g_h2.waves == 8) return false;  // (the eight-wave A/B geometry has no GNB instantiation)
+  if (g_tune.waves == 8) return false;  // (the eight-wave A/B geometry has no GNB instantiation)
   int bm = H2_BM;
   if (h16) {
     bool r16 = false;
     if (conv_h16_bm128(a, hout, wout, &r16)) {
       bm = 128;
-      if (g_h2.gnb == 2) return false;  // (A/B mode: only the two-workgroups-per-CU 64-cout kernels, whose epilogue runs under the other workgroup's K loop)
+      if (g_tune.gnb_mode() == 2) return false;  // (A/B mode: only the two-workgroups-per-CU 64-cout kernels, whose epilogue runs under the other workgroup's K loop)
     } else {  // the launcher's 32-cout workgroups for small grids have no GNB form
       const int cout_pad = (a->cout + 63) / 64 * 64;
       const bool nt4 = conv_h2_rows16(a, hout, wout);
       const int grid = (wout / H2_TW) * (hout / (nt4 ? 16 : 8)) * a->n * (cout_pad / H2_BM);
-      if (g_h2.bm32_small && !nt4 && grid <= H2_CUS / 2) return false;
-      if (g_h2.bm32 && a->c0 + a->c1 <= 128 && grid >= g_h2.bm32_min) return false;
+      if (g_tune.bm32_small && !nt4 && grid <= H2_CUS / 2) return false;
+      if (g_tune.bm32_on() && a->c0 + a->c1 <= 128 && grid >= g_tune.bm32_min()) return false;
     }
   }
   // the two x tensors meet between two 32-channel slabs of a tile (the epilogue reads x slab by slab: the 64 + 64 concat of the
   // outermost up block under 128-cout workgroups; key 37 = 3: only between two tiles, round 6's first rule -- such calls then lose
   // the epilogue to a statistics pass over x and dA per half, 2 x 0.5 ms per conv at batch 128)
-  if (a->gnb_x1 != nullptr && (a->gnb_c0 <= 0 || a->gnb_c0 >= a->cout || a->gnb_c0 % (g_h2.gnb_seam64 ? 32 : bm) != 0)) return false;
+  if (a->gnb_x1 != nullptr && (a->gnb_c0 <= 0 || a->gnb_c0 >= a->cout || a->gnb_c0 % (g_tune.gnb_seam64() ? 32 : bm) != 0)) return false;
   return true;
 }
 
 int conv_h2_stats_tiles(const dsg_conv_args* a, int hout, int wout) {
-  if (!g_h2.stats || !conv_h2_eligible(a, hout, wout)) return 0;
+  if (!g_tune.stats || !conv_h2_eligible(a, hout, wout)) return 0;
   if (a->splitk_ws) {  // the split-K path's reduce pass writes its own (coarser) partials
     int sp = 1;
     if (conv_h2_splitk_slices(a, hout, wout, &sp) > 1) return sp;
@@ -372,31 +370,6 @@ int conv_h2_launch(const dsg_conv_args* a, int hout, int wout, hipStream_t st) {
   if (a->compute_dtype == DSG_F16) return conv_h2_launch_f16(a, hout, wout, st);
   return conv_h2_launch_t<0>(a, hout, wout, st);
 }
-
-void conv_h2_set_enabled(int on) { g_h2.enabled = on; ++g_h2.epoch; }
-void conv_h2_set_rows(int r) { g_h2.rows = r; ++g_h2.epoch; }
-void conv_h2_set_stats(int on) { g_h2.stats = on; ++g_h2.epoch; }
-void conv_h2_set_fold(int on) { g_h2.fold = on; ++g_h2.epoch; }
-void conv_h2_set_waves(int w) { g_h2.waves = w; ++g_h2.epoch; }
-void conv_h2_set_pw_occ2(int v) { g_h2.pw_occ2 = v; ++g_h2.epoch; }
-void conv_h2_set_s2(int v) { g_h2.s2 = v; ++g_h2.epoch; }
-void conv_h2_set_bm32_small(int v) { g_h2.bm32_small = v; ++g_h2.epoch; }
-void conv_h2_set_bm32(int v) { g_h2.bm32 = v != 0; if (v > 1) g_h2.bm32_min = v; ++g_h2.epoch; }
-void conv_h2_set_bm128(int v) { g_h2.bm128 = v; ++g_h2.epoch; }
-void conv_h2_set_splitk(int v) { g_h2.splitk = v; ++g_h2.epoch; }
-void conv_h2_set_ws2(int v) { g_h2.ws2 = v; ++g_h2.epoch; }
-void conv_h2_set_fuse_sc(int v) { g_h2.fuse_sc = v; ++g_h2.epoch; }
-void conv_h2_set_pre(int v) { g_h2.pre = v; ++g_h2.epoch; }
-void conv_h2_set_narrow(int v) { g_h2.narrow = v; ++g_h2.epoch; }
-void conv_h2_set_splitk_mid(int v) { g_h2.splitk_mid = v; ++g_h2.epoch; }
-void conv_h2_set_rows_rule(int v) { g_h2.rows_rule = v; ++g_h2.epoch; }
-void conv_h2_set_gnb_bm64(int v) { g_h2.gnb_bm64 = v; ++g_h2.epoch; }
-void conv_h2_set_s2_nchw(int v) { g_h2.s2_nchw = v; ++g_h2.epoch; }
-void conv_h2_set_gnb(int v) { g_h2.gnb = v == 3 ? 1 : v; g_h2.gnb_seam64 = v != 3; ++g_h2.epoch; }
-void conv_h2_set_pre_min_ct(int v) { g_h2.pre_min_ct = v > 0 ? v : 1; ++g_h2.epoch; }
-int conv_h2_get_fuse_sc() { return g_h2.fuse_sc; }
-int conv_in_tuning_epoch();  // conv_in.hip: its on/off switch moves the plan's statistics buffers too
-int conv_h2_tuning_epoch() { return g_h2.epoch + conv_in_tuning_epoch(); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Weight packing: OIHW fp32 (the checkpoint layout) -> the kernel's operand image

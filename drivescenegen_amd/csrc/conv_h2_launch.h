@@ -2,6 +2,7 @@
 // conv_h2.hip (PREC 0: fp32 tensors, fp16x2-split products), conv_h2_bf16.hip (PREC 1), conv_h2_f16.hip (PREC 2).
 #pragma once
 #include "conv_h2_kernel.h"
+#include "tuning.h"
 
 // 16-bit modes, 16-row tiles: workgroups the kernel is compiled to fit per CU (2: half the register file each -- one's
 // patch loads and output stores run under the other's MFMAs; A/B with tools/build_variant.sh)
@@ -11,38 +12,6 @@
 
 namespace dsg {
 
-// kernel-selection switches (dsg_set_tuning); defined in conv_h2.hip
-struct H2Tuning {
-  int enabled = 1;
-  int waves = 4;        // 16-row tiles: 4 waves x 4 rows or 8 waves x 2 rows (tuning key 6)
-  int fold = 1;         // folded up-sampler convs (key 8: A/B against the x2 gather)
-  int stats = 1;        // epilogue GroupNorm statistics (key 5: A/B against the separate pass)
-  int bm32 = 0;         // 32-cout x 8-row workgroups, two per CU, for the shallow levels (key 16; measured slower than
-                        // the 64 x 16 geometry: 0.356 vs 0.302 ms at 64 channels / 256^2 -- off)
-  int bm32_min = 512;   // ... when the 64-cout x 16-row grid has at least this many workgroups
-  int bm32_small = 1;   // 32-cout workgroups for grids of at most half the CUs (key 17)
-  int s2 = 1;           // stride-2 convs on the split path (key 15: A/B against the f32 MFMA kernel)
-  int pw_occ2 = 1;      // pointwise convs: 8-row tiles compiled for two workgroups per CU (key 11)
-  int rows = 0;         // rows per wave: 0 = by grid size, 2 | 4 forced (key 3)
-  int bm128 = 1;        // 16-bit modes: 128-cout workgroups where the grid still fills the chip (key 18)
-  int splitk = 1;       // split-K for grids of at most half the CUs, when the caller gives scratch (key 19)
-  int ws2 = 1;          // fp32-equivalent 3x3 convs with cin <= 128: 8-row tiles, one weight slab, two workgroups per CU (key 20)
-  int fuse_sc = 1;      // resnet shortcuts fused into conv2's K loop (key 23: A/B against the separate 1x1 kernel)
-  int splitk_mid = 1;   // split-K also for grids of 129 .. 170 workgroups with K >= 24 chunks: 3 slices (key 34)
-  int narrow = 1;       // maps narrower than a tile (16 x 16, 8 x 8) also take split-K, the folded up-sampler and the stride-2 kernel
-                        // (key 32: 0 = one-slice plain kernel / exact f32 MFMA kernels for them, the rule before round 4)
-  int pre = 1;          // pre-staged operand images for the layers with >= pre_min_ct cout tiles per patch (key 26)
-  int pre_min_ct = 16;  // ... (key 27: the threshold.  Measured, profiles/r03_operand_ablation.txt: at 4 -- every conv of the 256- / 512-channel
-                        // levels -- the convs gain 8.5 % and the prepare passes cost what they gain; at 16 only the folded up-samplers of
-                        // those levels qualify, whose patch is staged by 16-32 workgroups)
-  int gnb = 1;          // GroupNorm-backward statistics from the data-gradient conv's epilogue (key 37: A/B against the statistics pass)
-  int s2_nchw = 1;      // stride-2 convs of fp32 [N,C,H,W] tensors on the space-to-depth kernel too (key 40: A/B against the exact f32 kernel)
-  int gnb_bm64 = 1;     // 16-bit data-gradient convs with the GNB epilogue on 64-cout workgroups, two per CU (key 41: 0 = 128-cout ones where the plain conv takes them)
-  int gnb_seam64 = 1;   // ... also where the two x tensors meet inside a channel tile, at a multiple of 32 channels (key 37 = 3: off)
-  int rows_rule = 1;    // round 5's additions to the rows rule: 16-row tiles under three-slice split-K, 0.62 for the four-tap kernels (key 36)
-  int epoch = 0;        // bumped by every change: plans key their cached workspace sizes on it
-};
-extern H2Tuning g_h2;
 constexpr int H2_CUS = 256;
 
 bool conv_h2_fold(const dsg_conv_args* a);
@@ -103,7 +72,7 @@ int conv_h2_launch_t(const dsg_conv_args* a, int hout, int wout, hipStream_t st)
   constexpr int NP = PREC ? 1 : 2;
   const int hout0 = hout, wout0 = wout;  // the conv's own output map (the kernel may re-tile it)
   // pointwise: 8-row tiles, two workgroups per CU (the only pointwise kernels that take channel-blocked tensors)
-  const bool occ2 = a->ksize == 1 && (g_h2.pw_occ2 || a->src_layout || a->dst_layout);
+  const bool occ2 = a->ksize == 1 && (g_tune.pw_occ2 || a->src_layout || a->dst_layout);
   const bool nt4 = !occ2 && conv_h2_rows16(a, hout, wout);
   ConvH2P p;
   p.stats = a->stats_out;
@@ -177,7 +146,7 @@ int conv_h2_launch_t(const dsg_conv_args* a, int hout, int wout, hipStream_t st)
     p.split_stride = 0;
   }
   // shallow levels of the fp32-equivalent path: 64 couts x 8 rows, ONE weight slab, two workgroups per CU (see WS)
-  const bool ws2 = PREC == 0 && lay == 3 && g_h2.ws2 && !s2 && !fold && a->ksize == 3 && !a->upsample && p.cin <= 128 &&
+  const bool ws2 = PREC == 0 && lay == 3 && g_tune.ws2 && !s2 && !fold && a->ksize == 3 && !a->upsample && p.cin <= 128 &&
                    wout % H2_TW == 0 && slices == 1 &&
                    (wout / H2_TW) * (hout / 8) * p.n * (p.cout_pad / H2_BM) >= 2 * H2_CUS;
   // pre-staged operand image: the 16-row kernels' PRE form (the image holds what the staging pass would have produced)
@@ -203,7 +172,7 @@ int conv_h2_launch_t(const dsg_conv_args* a, int hout, int wout, hipStream_t st)
   }
 #define DSG_H2_LAUNCH(GM, KS, ACT)                                                  \
   do {                                                                              \
-    if (nt4 && g_h2.waves == 8) rc = h2_launch<GM, 2, KS, ACT, 8>(grid, lds, st, p); \
+    if (nt4 && g_tune.waves == 8) rc = h2_launch<GM, 2, KS, ACT, 8>(grid, lds, st, p); \
     else if (nt4) rc = h2_launch<GM, 4, KS, ACT>(grid, lds, st, p);                 \
     else rc = h2_launch<GM, 2, KS, ACT>(grid, lds, st, p);                          \
   } while (0)
@@ -223,8 +192,8 @@ int conv_h2_launch_t(const dsg_conv_args* a, int hout, int wout, hipStream_t st)
   // 32-cout workgroups: (a) optional, two per CU on the shallow levels (cin <= 128: LDS); (b) small batches: when
   // even the 8-row x 64-cout grid leaves more than half of the CUs idle, halve the cout tile to double the grid
   const bool bm32_ok = lay == 3 && !fold && !s2 && !k1 && !a->upsample && wout % H2_TW == 0 && (!sc || PREC == 0);
-  const bool bm32 = bm32_ok && ((g_h2.bm32 && p.cin <= 128 && (int)grid.x >= g_h2.bm32_min) ||
-                                (g_h2.bm32_small && !nt4 && (int)grid.x <= H2_CUS / 2 &&
+  const bool bm32 = bm32_ok && ((g_tune.bm32_on() && p.cin <= 128 && (int)grid.x >= g_tune.bm32_min()) ||
+                                (g_tune.bm32_small && !nt4 && (int)grid.x <= H2_CUS / 2 &&
                                  !(slices > 1 && splitk_prefers_bm64((int)grid.x, p.cin / H2_KC))));
   if (pre) {
     if constexpr (PREC == 0) {

@@ -15,6 +15,7 @@
 // max |w| -- and the result scaled back: no range requirement on x or w (the guard of DESIGN 4.4 is built in).
 // PREC 1 / 2: x and w rounded once to bf16 / fp16, one MFMA per product, as torch.autocast does for this conv.
 #include "dsg_h16.h"
+#include "tuning.h"
 
 namespace dsg {
 
@@ -32,11 +33,6 @@ struct ConvInP {
 };
 
 constexpr int CI_TH = 16, CI_TW = 32, CI_PH = CI_TH + 2, CI_PW = CI_TW + 2, CI_NPOS = CI_PH * CI_PW;
-
-static bool g_conv_in = true;
-static int g_conv_in_epoch = 0;
-void conv_in_set_enabled(int v) { g_conv_in = v != 0; ++g_conv_in_epoch; }
-int conv_in_tuning_epoch() { return g_conv_in_epoch; }
 
 __device__ __forceinline__ float pow2_scale_of(float m, float* back) {
   // s = 2^-e, *back = 2^e with e = exponent of m clamped to [-100, 100]; m == 0 / inf / nan -> 1
@@ -268,7 +264,7 @@ __global__ __launch_bounds__(256, PREC == 0 ? 2 : 3) void conv_in_kernel(ConvInP
 // shapes the kernel takes: 3x3, stride 1, one fp32 [N,C,H,W] source of at most 8 channels with no norm / temb / residual /
 // pool in the call, a channel-blocked result, 16 x 32 pixel tiles, cout in 32-channel tiles inside the weight stride
 bool conv_in_eligible(const dsg_conv_args* a, int hout, int wout) {
-  if (!g_conv_in) return false;
+  if (!g_tune.conv_in) return false;
   const int cin = a->c0 + a->c1;
   const int wstride = a->weight_cout_stride ? a->weight_cout_stride : a->cout;
   return a->ksize == 3 && a->stride == 1 && !a->upsample && !a->pool2 && a->c1 == 0 && cin <= 8 && a->src_layout == 0 &&

@@ -14,6 +14,7 @@
 // by the exact power of two of their max |w| first and the result scaled back (no range requirement on w); the activated
 // input is O(1) by construction (the call must carry a norm).  PREC 1 / 2: one bf16 / fp16 MFMA per product.
 #include "dsg_h16.h"
+#include "tuning.h"
 
 namespace dsg {
 
@@ -32,9 +33,6 @@ struct ConvOutP {
 
 constexpr int CO_TH = 16, CO_TW = 32, CO_PH = CO_TH + 2, CO_PW = CO_TW + 2, CO_NPOS = CO_PH * CO_PW;
 constexpr int CO_MAXC = 64;  // channels the weight fragments in LDS are sized for
-
-static bool g_conv_out = true;
-void conv_out_set_enabled(int v) { g_conv_out = v != 0; }
 
 __device__ __forceinline__ float co_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
@@ -243,7 +241,7 @@ __global__ __launch_bounds__(256, PREC == 0 ? 2 : 3) void conv_out_kernel(ConvOu
 // shapes the kernel takes: 3x3, stride 1, one channel-blocked source with a norm in the call, cin a multiple of 16 up to 64,
 // at most 8 output channels written as an fp32 [N,C,H,W] image, 16 x 32 pixel tiles
 bool conv_out_eligible(const dsg_conv_args* a, int hout, int wout) {
-  if (!g_conv_out) return false;
+  if (!g_tune.conv_out) return false;
   return a->ksize == 3 && a->stride == 1 && !a->upsample && !a->pool2 && a->c1 == 0 && a->c0 % 16 == 0 && a->c0 <= CO_MAXC &&
          a->src_layout == 1 && a->dst_layout == 0 && a->gn_scale_shift && !a->temb && !a->residual && !a->stats_out &&
          a->cout <= 8 && hout % CO_TH == 0 && wout % CO_TW == 0;

@@ -12,6 +12,7 @@
 // Concat, nearest-upsample, GroupNorm-apply+SiLU, bias, time-embedding add and residual add never
 // materialise: they are folded into the gather / epilogue of dsg_conv2d_fwd.
 #include "dsg_common.h"
+#include "tuning.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,7 +25,6 @@
 
 namespace dsg {
 int conv2d_fwd_impl(const dsg_conv_args* a, hipStream_t st, int force_direct);
-int conv_h2_tuning_epoch();
 int attention_fwd_exact(const float* qkv, float* out, int n, int c, int heads, int l, hipStream_t st);
 bool attention_blocked_ok(int c, int heads, int l);
 }
@@ -117,13 +117,6 @@ struct Param {
 
 }  // namespace
 
-namespace dsg {
-// intermediates of dsg_unet_forward in the channel-blocked layout (tuning key 13: A/B against [N,C,H,W])
-static int g_unet_blocked = 1;
-int unet_blocked() { return g_unet_blocked; }
-void unet_set_blocked(int v) { g_unet_blocked = v; }
-}  // namespace dsg
-
 struct dsg_unet {
   dsg_unet_config cfg;
   std::vector<void*> allocs;
@@ -138,7 +131,7 @@ struct dsg_unet {
   Res mid0, mid1;
   bool mid_attn = false;
   Att mid_att;
-  std::map<std::tuple<int, int, int>, size_t> ws_cache;  // (batch, blocked layout, tuning epoch) -> workspace bytes
+  std::map<std::tuple<int, int>, size_t> ws_cache;  // (batch, tuning epoch) -> workspace bytes
   std::string err;
   int dt() const { return cfg.compute_dtype; }  // dsg_dtype of the channel-blocked intermediates / matrix-core products
   // range guard of the weights (dsg_unet_set_param): max|w| of every uploaded conv weight lands in wmax_dev[param index],
@@ -512,7 +505,7 @@ struct Runner {
       if (!dry && dt() == DSG_F32 && dsg::zero_words(bound_base, (size_t)kBoundSlots * B, st) != hipSuccess)
         return rc = dsg::fail(DSG_ERR_HIP, "dsg_unet_forward: zero-fill launch failed");
     }
-    blocked = dsg::unet_blocked() != 0 || dt() != DSG_F32;  // (the 16-bit modes exist for channel-blocked tensors only)
+    blocked = dsg::g_tune.unet_blocked != 0 || dt() != DSG_F32;  // (the 16-bit modes exist for channel-blocked tensors only)
     for (int i = 0; i < cfg.num_blocks; ++i) blocked = blocked && cfg.block_out_channels[i] % 8 == 0;
     if (dt() != DSG_F32 && !blocked)
       return rc = dsg::fail(DSG_ERR_UNSUPPORTED_SHAPE, "dsg_unet_forward: the bf16 / fp16 modes need block_out_channels %% 8 == 0");
@@ -795,7 +788,7 @@ DSG_API int dsg_unet_workspace_bytes(dsg_unet_t* h, int32_t batch, size_t* bytes
   // (the layout and the kernel-selection switches decide which convs write statistics, hence the arena's layout)
   int rc0 = h->commit_ranges();  // (kernel selection, hence the arena, depends on the weights' range bits)
   if (rc0 != DSG_OK) return fail(rc0, "dsg_unet_workspace_bytes: reading the weight maxima back failed");
-  const auto key = std::make_tuple((int)batch, dsg::unet_blocked() ? 1 : 0, dsg::conv_h2_tuning_epoch());
+  const auto key = std::make_tuple((int)batch, dsg::g_tune.epoch);
   auto it = h->ws_cache.find(key);
   if (it == h->ws_cache.end()) {
     Runner r{h, batch, nullptr, true, nullptr};

@@ -5,6 +5,7 @@ the whole-network plan (dsg_unet_forward) instead.  GPU tensors only -- no fallb
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -306,6 +307,25 @@ def tuning_epoch() -> int:
     """dsg_tuning_epoch: advances with every accepted dsg_set_tuning call (a test hook) -- the key of host-side caches of
     kernel-selection answers."""
     return int(_lib.load().dsg_tuning_epoch())
+
+
+@contextlib.contextmanager
+def tuning(**switches):
+    """``with ops.tuning(splitk=0, gnb=3): ...`` -- kernel-selection switches (dsg_set_tuning, a test hook: DSG_TESTING=1)
+    by the names of csrc/tuning.h, for the body; on exit every switch gets back the value it had on entry."""
+    lib = _lib.load()
+    saved = []
+    try:
+        for name, value in switches.items():
+            key, old = C.c_int32(0), C.c_int32(0)
+            _lib.check(lib.dsg_tuning_key(name.encode(), C.byref(key)))
+            _lib.check(lib.dsg_get_tuning(key, C.byref(old)))
+            _lib.check(lib.dsg_set_tuning(key, int(value)))
+            saved.append((key.value, old.value))
+        yield
+    finally:
+        for key, old in reversed(saved):
+            _lib.check(lib.dsg_set_tuning(key, old))
 
 
 def conv_operand_prepare(src0, src1=None, gn_scale_shift=None, silu=False, src_bound=None, src_bound1=None):

@@ -688,7 +688,8 @@ int dsg_prof_dump(const char* csv_path);
 /* Kernel-selection switches for A/B measurements and tests -- a TEST HOOK, not part of the product surface: the call is
  * refused (DSG_ERR_INVALID_ARG) unless the process environment has DSG_TESTING=1, so a production process cannot change
  * process-global state through this header; what a deployment may want to choose per plan is in dsg_unet_config.flags.
- * (Defaults in brackets; python: env DSG_TUNING="key=value,..." implies DSG_TESTING=1.)
+ * The switches, their defaults and accepted values are ONE table, csrc/tuning.h; tests/test_tuning_cpu.py holds this list
+ * against it.  (Defaults in brackets; python: env DSG_TUNING="key=value,..." implies DSG_TESTING=1.)
  *   1  K-chunk of the fp32 conv kernel: [0 = by grid size] | 4 | 8
  *   2  fp16x2-split conv kernels: [1] | 0 = every contraction on the f32 MFMA
  *   3  rows per wave of the split conv kernel: [0 = by grid size: rounds of 256 workgroups] | 2 | 4 | 3 = by grid size, but never 16-row tiles
@@ -701,24 +702,40 @@ int dsg_prof_dump(const char* csv_path);
  *  11  pointwise split convs as 8-row tiles, two workgroups per CU: [1] | 0 = the 3x3 kernel's geometry
  *  13  dsg_unet_forward keeps its intermediate activations channel-blocked [N,C/8,H,W,8]: [1] | 0 = [N,C,H,W]
  *      (query dsg_unet_workspace_bytes again after changing it)
- *  17  blocked 3x3 convs whose 8-row x 64-cout grid covers at most half the CUs (small batches) as 32-cout
- *      workgroups: [1] | 0
+ *  14  attention with head_dim 8 on the matrix cores (fp16x2 split): [1] | 0 = the VALU kernel
+ *  15  stride-2 convs of channel-blocked tensors on the split path: [1] | 0 = the f32 MFMA kernel
  *  16  blocked 3x3 convs with cin <= 128 as 32-cout x 8-row workgroups, two per CU: [0] | 1 | n > 1 = when the
  *      64-cout x 16-row grid has at least n workgroups (1 = 512); bit-identical results, measured slower
+ *  17  blocked 3x3 convs whose 8-row x 64-cout grid covers at most half the CUs (small batches) as 32-cout
+ *      workgroups: [1] | 0
  *  18  16-bit modes: 3x3 convs with cout % 128 == 0 as 128-cout workgroups while the grid fills the chip: [1] | 0
  *  19  split-K for grids of at most half the CUs (needs dsg_conv_args.splitk_ws): [1] | 0
- *  25  dsg_unet_forward keeps q, k, v and the attention output channel-blocked (head_dim 8): [1] | 0
+ *  20  fp32-equivalent 3x3 convs with cin <= 128 on channel-blocked tensors: 8-row tiles with ONE weight slab in LDS,
+ *      two workgroups per CU (grids of at least 512 workgroups): [1] | 0
+ *  21  conv_in (fp32 [N,C<=8,H,W] image -> channel-blocked result, 16 x 32 pixel tiles, cout % 32 == 0) on its own kernel
+ *      with built-in operand scaling and GroupNorm statistics (csrc/conv_in.hip): [1] | 0 = the exact f32-MFMA kernel
+ *  22  conv_out (normalised channel-blocked source of <= 64 channels -> fp32 [N,C<=8,H,W] image, 16 x 32 pixel tiles) on its
+ *      own matrix-core kernel with per-output-channel weight scaling (csrc/conv_out.hip): [1] | 0 = the VALU / padded kernels
  *  23  resnet shortcuts fused into conv2's K loop (dsg_conv_args.sc_*): [1] | 0 (0: dsg_conv2d_fuses_shortcut answers no)
+ *  25  dsg_unet_forward keeps q, k, v and the attention output channel-blocked (head_dim 8): [1] | 0
+ *  26  fp32-equivalent 16-row 3x3 convs read a pre-staged operand image (dsg_conv_args.src_operand, dsg_conv_operand_prepare)
+ *      where one patch serves enough cout tiles (key 27): [1] | 0 = dsg_conv2d_takes_operand answers no, every kernel stages its own patch
+ *  27  the threshold of key 26: cout tiles (of 64; x 4 phases for the folded up-sampler) per staged patch from which a layer
+ *      asks for the image: [16] | n >= 1
+ *  29  16-bit 3x3 weight gradients with cout % 128 == 0 as 64 ci x 128 co workgroups (a wave keeps two co tiles, one
+ *      workgroup per CU): [1] | 0 = 64 x 64 workgroups, two per CU
  *  30  16-bit pointwise weight gradients on a kernel of their own (tiles up to 128 ci x 128 co): [1] | 0 = the 3x3 kernel's
  *      one-tap instantiation (64 x 64 workgroups)
+ *  31  fp32-equivalent 3x3 weight gradients with cout % 128 == 0 as 32 ci x 128 co workgroups (a wave keeps two co tiles, nine
+ *      (tap, co tile) units on every wave; conv_wgrad_h2w_kernel): [1] | 0 = the 32 ci x 64 co workgroup everywhere
+ *  32  maps narrower than a 32-column tile (16 x 16, 8 x 8: the deepest levels of BASELINE configs[3]'s 512 x 512 network) also
+ *      take split-K, the folded up-sampler kernel and the stride-2 space-to-depth kernel: [1] | 0 = one-slice plain kernel and
+ *      the exact f32-MFMA kernels for them
  *  34  split-K also for grids of 129 .. 170 workgroups with at least 24 K-chunks (batch-5 sampling at the 32 x 32 level): three
  *      slices = two rounds of a third of the work: [1] | 0 = only grids of at most half the CUs split
  *  36  round 5's additions to the rows-per-wave rule (key 3 = 0): 16-row tiles for the convs that split K in three slices (one
  *      round of 195 .. 255 workgroups instead of two), and the four-tap kernels (folded up-sampler) priced at 0.62 of a 16-row
  *      workgroup per 8-row one instead of 0.55: [1] | 0
- *  32  maps narrower than a 32-column tile (16 x 16, 8 x 8: the deepest levels of BASELINE configs[3]'s 512 x 512 network) also
- *      take split-K, the folded up-sampler kernel and the stride-2 space-to-depth kernel: [1] | 0 = one-slice plain kernel and
- *      the exact f32-MFMA kernels for them
  *  37  GroupNorm-backward statistics from the data-gradient conv's epilogue (dsg_conv_args.gnb_*): [1] | 0 = dsg_conv2d_gnb_supported
  *      answers no (the statistics pass runs) | 2 = only the 64-cout workgroups carry the epilogue | 3 = as 1, but a call whose two
  *      x tensors meet INSIDE a channel tile (at a multiple of 32 channels) loses the epilogue (round 6's first rule)
@@ -726,27 +743,20 @@ int dsg_prof_dump(const char* csv_path);
  *  39  16-bit weight gradient of Upsample2D's conv in the folded form -- x's own map as the K grid, dY read as its space-to-depth
  *      image, the 2 x 2 taps a pixel parity reads: 16 products per low-resolution pixel instead of 36: [1] | 0 = nine taps at full
  *      resolution with x addressed at (y >> 1, x >> 1)
- *  41  16-bit data-gradient convs with the GroupNorm-backward epilogue (gnb_*) on 64-cout workgroups, two per CU, whatever the
- *      plain conv would take: [1] | 0 = 128-cout workgroups where cout % 128 == 0 and the grid fills the chip (round 6's first form)
  *  40  stride-2 3x3 convs of fp32 [N,C,H,W] tensors (weight_h2_s2 given: the fp32 training tape's down-samplers) on the
  *      space-to-depth kernel, as the channel-blocked ones: [1] | 0 = the exact f32 MFMA kernel
- *  31  fp32-equivalent 3x3 weight gradients with cout % 128 == 0 as 32 ci x 128 co workgroups (a wave keeps two co tiles, nine
- *      (tap, co tile) units on every wave; conv_wgrad_h2w_kernel): [1] | 0 = the 32 ci x 64 co workgroup everywhere
- *  29  16-bit 3x3 weight gradients with cout % 128 == 0 as 64 ci x 128 co workgroups (a wave keeps two co tiles, one
- *      workgroup per CU): [1] | 0 = 64 x 64 workgroups, two per CU
- *  20  fp32-equivalent 3x3 convs with cin <= 128 on channel-blocked tensors: 8-row tiles with ONE weight slab in LDS,
- *      two workgroups per CU (grids of at least 512 workgroups): [1] | 0
- *  21  conv_in (fp32 [N,C<=8,H,W] image -> channel-blocked result, 16 x 32 pixel tiles, cout % 32 == 0) on its own kernel
- *      with built-in operand scaling and GroupNorm statistics (csrc/conv_in.hip): [1] | 0 = the exact f32-MFMA kernel
- *  22  conv_out (normalised channel-blocked source of <= 64 channels -> fp32 [N,C<=8,H,W] image, 16 x 32 pixel tiles) on its
- *      own matrix-core kernel with per-output-channel weight scaling (csrc/conv_out.hip): [1] | 0 = the VALU / padded kernels
- *  15  stride-2 convs of channel-blocked tensors on the split path: [1] | 0 = the f32 MFMA kernel
- *  14  attention with head_dim 8 on the matrix cores (fp16x2 split): [1] | 0 = the VALU kernel */
+ *  41  16-bit data-gradient convs with the GroupNorm-backward epilogue (gnb_*) on 64-cout workgroups, two per CU, whatever the
+ *      plain conv would take: [1] | 0 = 128-cout workgroups where cout % 128 == 0 and the grid fills the chip (round 6's first form) */
 int dsg_set_tuning(int32_t key, int32_t value);
 /* A counter that advances with every accepted dsg_set_tuning call, whichever kernel family the key belongs to (0 in a
  * production process): host-side caches of kernel-selection answers (dsg_conv2d_fuses_shortcut, dsg_conv2d_takes_operand,
  * dsg_unet_workspace_bytes) key on it. */
 int32_t dsg_tuning_epoch(void);
+/* Read-only companions of dsg_set_tuning; they need no DSG_TESTING and change no state.  dsg_get_tuning: the value last
+ * accepted for `key`, or its default (DSG_ERR_INVALID_ARG for a key the list above does not have).  dsg_tuning_key: the key
+ * of the switch whose field in csrc/tuning.h is called `name` ("splitk" -> 19), so that tests and tools name switches, not numbers. */
+int dsg_get_tuning(int32_t key, int32_t* value);
+int dsg_tuning_key(const char* name, int32_t* key);
 
 #ifdef __cplusplus
 }

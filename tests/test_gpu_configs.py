@@ -261,24 +261,20 @@ def test_reference_evaluate_call_750_steps_teacher_forced():
 
 def test_generation_batch5_forward_vs_live_oracle_and_selection_rules():
     """generation.py:14-20 samples at batch 5 on the train.py:39-57 network: at that batch the 32 x 32 level runs the
-    three-slice split-K with 16-row tiles and the 64 x 64 level the 64-cout slices (tuning key 36, default on; ADVICE r05: no
+    three-slice split-K with 16-row tiles and the 64 x 64 level the 64-cout slices (the rows_rule switch, default on; ADVICE r05: no
     whole-net check existed at this batch).  One forward of 5 different x_t at 5 timesteps against the LIVE CPU oracle
-    (rel-L2 <= 1e-4 per row), and key 36 = 0 (the round-4 selection) gives the same eps BIT FOR BIT: at this batch
+    (rel-L2 <= 1e-4 per row), and rows_rule = 0 (the round-4 selection) gives the same eps BIT FOR BIT: at this batch
     the rule changes tile HEIGHT under the same three K slices, and tile geometry never changes a bit (per-pixel summation
     order and the 8 x 32 statistics tiles are geometry-independent by construction)."""
-    from drivescenegen_amd import _lib
+    from drivescenegen_amd import ops
     net = synth_weights(d.UNet2DModel(**DEFAULT3)).to(DEV).eval().requires_grad_(False)
     ora = synth_weights(OracleUNet2DModel(**DEFAULT3)).eval()
     x = noisy_inputs(DEFAULT3, 5)
     t = torch.tensor([749, 500, 250, 20, 0])
-    lib = _lib.load()
     got = {}
-    try:
-        for on in (1, 0):
-            _lib.check(lib.dsg_set_tuning(36, on))
+    for on in (1, 0):
+        with ops.tuning(rows_rule=on):
             got[on] = net(x.to(DEV), t.to(DEV)).sample.cpu()
-    finally:
-        lib.dsg_set_tuning(36, 1)
     with torch.no_grad():
         want = ora(x, t).sample
     for i in range(5):

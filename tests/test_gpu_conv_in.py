@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from drivescenegen_amd import _lib, ops, synth  # noqa: E402
+from drivescenegen_amd import ops, synth  # noqa: E402
 
 DEV = "cuda"
 
@@ -44,13 +44,9 @@ def test_conv_in_fp32_equivalent_vs_fp64(cin, cout, h, w, n):
     assert torch.allclose(st.sum(dim=2), ref, rtol=3e-6, atol=1e-4), float((st.sum(dim=2) - ref).abs().max())
     t0 = got[:, :, :16, :32].double()
     assert torch.allclose(st[:, :, 0, 0], t0.sum(dim=(2, 3)), rtol=3e-6, atol=1e-4)
-    # same values as the exact f32-MFMA kernel that served the call before (tuning key 21 switches this kernel off)
-    lib = _lib.load()
-    _lib.check(lib.dsg_set_tuning(21, 0))
-    try:
+    # same values as the exact f32-MFMA kernel that served the call before (the conv_in switch turns this kernel off)
+    with ops.tuning(conv_in=0):
         old, st_old = _run(x, wt, b)
-    finally:
-        _lib.check(lib.dsg_set_tuning(21, 1))
     assert st_old is None  # (that kernel writes no statistics: the plan then runs a pass of its own)
     assert ((got - old).abs().double() <= 6e-7 * bound).all()
     assert not torch.equal(got, old)

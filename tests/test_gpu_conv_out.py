@@ -10,7 +10,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from drivescenegen_amd import _lib, ops, synth  # noqa: E402
+from drivescenegen_amd import ops, synth  # noqa: E402
 
 DEV = "cuda"
 
@@ -49,13 +49,9 @@ def test_conv_out_fp32_equivalent_vs_fp64(cin, cout, h, w, n):
     assert got.shape == want.shape and torch.isfinite(got).all()
     err = (got.double() - want).abs()
     assert (err <= 1e-6 * bound).all(), float((err / bound).max())
-    # the kernel that served the call before (tuning key 22 switches this one off) gives the same values to round-off
-    lib = _lib.load()
-    _lib.check(lib.dsg_set_tuning(22, 0))
-    try:
+    # the kernel that served the call before (the conv_out switch turns this one off) gives the same values to round-off
+    with ops.tuning(conv_out=0):
         old, *_ = _case(cin, cout, h, w, n)
-    finally:
-        _lib.check(lib.dsg_set_tuning(22, 1))
     assert ((got - old).abs().double() <= 2e-6 * bound).all()
     assert not torch.equal(got, old)
 

@@ -9,7 +9,7 @@ bound, for every kernel geometry that takes the fusion (16-row tiles, 8-row tile
 single and concatenated shortcut sources; (b) against the unfused pair of calls (1x1, then 3x3 with residual) -- same
 value up to the one extra rounding the unfused path has; (c) the range guard on the raw source at |x| ~ 1e5 / 1e-7 per
 image; (d) batch independence: row i of a batch is bitwise the batch-1 call; (e) the GroupNorm statistics it leaves;
-(f) the whole network with and without the fusion (dsg_set_tuning key 23)."""
+(f) the whole network with and without the fusion (ops.tuning(fuse_sc=0))."""
 import zlib
 
 import numpy as np
@@ -20,7 +20,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import drivescenegen_amd as d  # noqa: E402
-from drivescenegen_amd import _lib, ops, synth  # noqa: E402
+from drivescenegen_amd import ops, synth  # noqa: E402
 from tests.common import CFG1, CFG2, noisy_inputs, rel_l2, same_kernels_at_any_batch, synth_weights  # noqa: E402
 
 DEV = "cuda"
@@ -182,7 +182,7 @@ def test_fused_shortcut_under_split_k(name, shape):
                                               ("b1_bm64_4slices", (1, 512, 256, 512, 256, 64, 64), False),
                                               ("b1_bm64_4slices_fused", (1, 512, 256, 512, 256, 64, 64), True)])
 def test_tile_height_rule_and_64_cout_slices_keep_the_values(name, shape, fused):
-    """the selection rules of tuning key 36 are default-on and had no numeric test.  (i) batch-5 sampling at the
+    """the selection rules of the rows_rule switch are default-on and had no numeric test.  (i) batch-5 sampling at the
     32 x 32 level (generation.py:14-20): 129..170 eight-row tiles with long K take THREE K slices of 16-row tiles (NT = 4
     kernels, the fused-shortcut form included); (ii) batch 1 at the 64 x 64 level with >= 24 chunks of K: 64-cout workgroups with
     four slices instead of 32-cout workgroups with two.  Key 36 = 0 is the round-4 selection.  Both settings against fp64 in
@@ -193,18 +193,14 @@ def test_tile_height_rule_and_64_cout_slices_keep_the_values(name, shape, fused)
     case = _case(n, c, cout, sc0, sc1, h, w, seed=zlib.crc32(name.encode()) % 1000)
     ref = _ref64(*case)
     scale = _bound_sum(case[0], case[1], case[2], case[3], case[4], case[7]) + 1e-30
-    lib = _lib.load()
     got = {}
-    try:
-        for on in (0, 1):
-            _lib.check(lib.dsg_set_tuning(36, on))
+    for on in (0, 1):
+        with ops.tuning(rows_rule=on):
             got[on] = _run(*case, fused=fused, want_stats=True, splitk=True)
-    finally:
-        lib.dsg_set_tuning(36, 1)
     if n == 5:
         assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
     else:
-        assert not torch.equal(got[0][0], got[1][0]), "key 36 did not change the K slicing of this shape"
+        assert not torch.equal(got[0][0], got[1][0]), "the rows_rule switch did not change the K slicing of this shape"
     for on in (0, 1):
         y, st = got[on]
         assert torch.isfinite(y).all()
@@ -231,19 +227,15 @@ def test_shapes_that_do_not_fuse_say_so():
 
 @pytest.mark.parametrize("cfg_name,cfg,batch", [("cfg1", CFG1, 2), ("cfg2", CFG2, 2)])
 def test_whole_net_with_and_without_the_fusion(cfg_name, cfg, batch):
-    """dsg_unet_forward with the shortcuts fused (default) and as separate 1x1 calls (tuning key 23 = 0): the same eps to
+    """dsg_unet_forward with the shortcuts fused (default) and as separate 1x1 calls (fuse_sc = 0): the same eps to
     fp32 round-off; each is separately held to the oracle tolerance by the other suites."""
-    lib = _lib.load()
     net = synth_weights(d.UNet2DModel(**cfg)).to(DEV).eval().requires_grad_(False)
     x = noisy_inputs(cfg, batch).to(DEV)
     t = torch.tensor([980, 20][:batch], device=DEV)
     with same_kernels_at_any_batch():
         fused = net(x, t).sample.clone()
-        try:
-            _lib.check(lib.dsg_set_tuning(23, 0))
+        with ops.tuning(fuse_sc=0):
             plain = net(x, t).sample.clone()
-        finally:
-            lib.dsg_set_tuning(23, 1)
     assert torch.isfinite(fused).all()
     assert rel_l2(fused.cpu(), plain.cpu()) <= 5e-6, rel_l2(fused.cpu(), plain.cpu())
     if cfg_name == "cfg2":
@@ -302,15 +294,11 @@ def test_fused_shortcut_16bit_modes(name, mode):
 
 def test_whole_net_bf16_with_and_without_the_fusion():
     from tests.common import CFG5
-    lib = _lib.load()
     net = synth_weights(d.UNet2DModel(**CFG5)).to(DEV).eval().requires_grad_(False).set_compute_dtype("bf16")
     x = noisy_inputs(CFG5, 2).to(DEV)
     t = torch.tensor([980, 20], device=DEV)
     fused = net(x, t).sample.clone()
-    try:
-        _lib.check(lib.dsg_set_tuning(23, 0))
+    with ops.tuning(fuse_sc=0):
         plain = net(x, t).sample.clone()
-    finally:
-        lib.dsg_set_tuning(23, 1)
     assert torch.isfinite(fused).all() and not torch.equal(fused, plain)
     assert rel_l2(fused.cpu(), plain.cpu()) <= 1e-2   # two bf16 evaluations of the same net (each <= 2e-2 of the fp32 oracle)

@@ -13,7 +13,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from drivescenegen_amd import _lib, ops, synth  # noqa: E402
+from drivescenegen_amd import ops, synth  # noqa: E402
 
 DEV = "cuda"
 GROUPS = 32
@@ -69,12 +69,10 @@ CASES = [
 
 @pytest.fixture(params=[1, 0], ids=["gnb_on_64_cout_workgroups", "gnb_on_128_cout_workgroups"])
 def gnb_workgroups(request):
-    """dsg_set_tuning key 41: the 16-bit GNB data gradients run on 64-cout workgroups by default; 0 lets them take the 128-cout
+    """The gnb_bm64 switch: the 16-bit GNB data gradients run on 64-cout workgroups by default; 0 lets them take the 128-cout
     ones the case names describe (both instantiations stay covered)"""
-    lib = _lib.load()
-    _lib.check(lib.dsg_set_tuning(41, request.param))
-    yield request.param
-    lib.dsg_set_tuning(41, 1)
+    with ops.tuning(gnb_bm64=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
@@ -159,54 +157,42 @@ def test_shapes_without_the_form_say_so_and_the_switch_turns_it_off():
     assert not ask(1, 64, 64, 0, 32, 32)[0]            # a grid of at most half the chip: the 32-cout workgroups have no GNB form
     # cat(192, 64) / configs[0]'s cat(64, 32) / cat(96, 32): the x tensors do not meet at a multiple of 128 channels -- such calls
     # run on 64-cout workgroups, and where the seam falls inside one of those (96 | 32) the epilogue reads x slab by slab (32
-    # channels) from the tensor that holds it (values: test_query_and_dispatch_agree_over_a_shape_sweep); key 37 = 3 refuses
+    # channels) from the tensor that holds it (values: test_query_and_dispatch_agree_over_a_shape_sweep); gnb = 3 refuses
     # them, as round 6's first rule did
     assert ask(8, 64, 192, 64, 64, 64)[0] and ask(16, 32, 64, 32, 64, 64)[0] and ask(8, 64, 96, 32, 64, 64)[0]
-    lib = _lib.load()
-    try:
-        _lib.check(lib.dsg_set_tuning(37, 3))
+    with ops.tuning(gnb=3):
         assert not ask(8, 64, 96, 32, 64, 64)[0]           # the seam inside a 64-cout tile
-        assert ask(8, 64, 192, 64, 64, 64)[0]              # ... between two 64-cout tiles (key 41: the GNB calls' workgroups)
-        _lib.check(lib.dsg_set_tuning(41, 0))              # ... inside a 128-cout one
-        yes, (dyb, gnb, kw) = ask(8, 64, 192, 64, 64, 64)
-        assert not yes
-        with pytest.raises(RuntimeError, match="GroupNorm-backward epilogue"):
-            ops.conv2d_fused(dyb, None, gnb=gnb, want_stats=True, **kw)
-        assert ask(8, 64, 128, 0, 64, 64)[0]
-    finally:
-        lib.dsg_set_tuning(37, 1)
-        lib.dsg_set_tuning(41, 1)
+        assert ask(8, 64, 192, 64, 64, 64)[0]              # ... between two 64-cout tiles (gnb_bm64: the GNB calls' workgroups)
+        with ops.tuning(gnb_bm64=0):                       # ... inside a 128-cout one
+            yes, (dyb, gnb, kw) = ask(8, 64, 192, 64, 64, 64)
+            assert not yes
+            with pytest.raises(RuntimeError, match="GroupNorm-backward epilogue"):
+                ops.conv2d_fused(dyb, None, gnb=gnb, want_stats=True, **kw)
+            assert ask(8, 64, 128, 0, 64, 64)[0]
     assert not ask(8, 64, 112, 16, 64, 64)[0]          # cat(112, 16): the seam is inside a 32-channel slab
     assert not ask(8, 64, 128, 0, 64, 48)[0]           # not a multiple of 32 columns
-    try:
-        _lib.check(lib.dsg_set_tuning(37, 0))
+    with ops.tuning(gnb=0):
         assert not ask(8, 64, 128, 0, 64, 64)[0]
-    finally:
-        lib.dsg_set_tuning(37, 1)
 
 
 @pytest.mark.parametrize("dtn", ["fp32", "bf16"])
 def test_training_step_gradients_with_and_without_the_epilogue_statistics(dtn):
-    """The whole backward walk on configs[0]'s network at a batch large enough for the GNB kernels (tuning key 37 = 1, default)
-    against key 37 = 0 (the statistics pass): the same loss bit for bit (the forward is untouched), every gradient equal to
+    """The whole backward walk on configs[0]'s network at a batch large enough for the GNB kernels (gnb = 1, default)
+    against gnb = 0 (the statistics pass): the same loss bit for bit (the forward is untouched), every gradient equal to
     summation-order round-off."""
     import drivescenegen_amd as d
     from tests.common import CFG1, synth_weights
-    lib = _lib.load()
     grads = {}
     x0 = torch.from_numpy(synth.synth_scene_rasters(16, 3, 64, 64, 3)).to(DEV)
     nz = torch.from_numpy(synth.normal(4, (16, 3, 64, 64))).to(DEV)
     t = torch.arange(16, device=DEV) * 60
     sch = d.DDPMScheduler()
-    try:
-        for on in (1, 0):
-            _lib.check(lib.dsg_set_tuning(37, on))
+    for on in (1, 0):
+        with ops.tuning(gnb=on):
             net = synth_weights(d.UNet2DModel(**CFG1)).to(DEV).train().set_compute_dtype(dtn)
             loss = d.mse_loss(net(sch.add_noise(x0, nz, t), t, return_dict=False)[0], nz)
             loss.backward()
             grads[on] = (float(loss.detach()), {k: p.grad.detach().clone() for k, p in net.named_parameters()})
-    finally:
-        lib.dsg_set_tuning(37, 1)
     assert grads[0][0] == grads[1][0]
     # the whole gradient vector, and every tensor that is not itself rounding noise (a 16-bit tape leaves ~1e-2 of a layer's
     # typical gradient as noise on the tensors whose true gradient nearly cancels)
@@ -222,7 +208,7 @@ def test_training_step_gradients_with_and_without_the_epilogue_statistics(dtn):
             r = _rel(grads[1][1][k], grads[0][1][k])
             if r > worst:
                 worst, worst_key = r, k
-    assert differ > 0, "key 37 changed nothing: no layer of this net took the GNB kernel at this batch"
+    assert differ > 0, "the gnb switch changed nothing: no layer of this net took the GNB kernel at this batch"
     assert whole <= (1e-4 if dtn == "fp32" else 5e-3), whole
     assert worst <= (2e-4 if dtn == "fp32" else 2e-2), (worst, worst_key)
 

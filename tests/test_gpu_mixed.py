@@ -184,7 +184,7 @@ def test_conv_in_fp32_image_to_blocked16(mode, cin):
 def test_conv_out_blocked16_to_fp32_image(mode, cout):
     """conv_out: GroupNorm + SiLU folded in front, 16-bit blocked sources -> fp32 [N,C,H,W] on csrc/conv_out.hip: the
     activated input and the weights are rounded once to the 16-bit type, as torch.autocast does for this conv
-    (tests/test_gpu_conv_out.py has the kernel's own cases; with tuning key 22 off: cout 8 on the zero-padded matrix-core
+    (tests/test_gpu_conv_out.py has the kernel's own cases; with the conv_out switch off: cout 8 on the zero-padded matrix-core
     kernel, cout <= 4 on the VALU kernel, which keeps the activated values in fp32)."""
     n, c, h, w = 2, 64, 32, 64
     xq = _rnd(_t(31, (n, c, h, w)), mode)

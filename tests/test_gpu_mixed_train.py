@@ -76,11 +76,10 @@ def test_wgrad16_sampler_convs_read_the_half_resolution_operand_in_place(case, m
     Upsample2D's conv (train.py:39-57's up blocks: nearest x2 then 3x3) reads the LOW-resolution x -- the tape used to write a
     4x larger upsampled tensor first; Downsample2D's stride-2 conv takes dY as zero between its pixels -- the tape used to copy
     dY into a zeroed full-resolution buffer with a strided torch copy.  Against fp64 on the same rounded operands; the nine-tap
-    forms (x at (y >> 1, x >> 1): dsg_set_tuning key 39 = 0 for the up-sampler) bitwise against the old route (the same kernel
-    on the materialised tensors: the products and their order are the same); the up-sampler's folded form (key 39 = 1, the
+    forms (x at (y >> 1, x >> 1): wgrad16_fold = 0 for the up-sampler) bitwise against the old route (the same kernel
+    on the materialised tensors: the products and their order are the same); the up-sampler's folded form (wgrad16_fold = 1, the
     default: x's own map as the K grid, dY as its space-to-depth image, 4 taps per pixel parity) against fp64 and the nine-tap
     form."""
-    from drivescenegen_amd import _lib
     _, kind, cin, cout, h, w, n = case          # (h, w): x's map
     x = _rnd(_t(11, (n, cin, h, w)), mode)
     xb = ops.to_blocked(x.to(DEV), mode)
@@ -93,11 +92,8 @@ def test_wgrad16_sampler_convs_read_the_half_resolution_operand_in_place(case, m
         ref = torch.nn.grad.conv2d_weight(F.interpolate(x.double(), scale_factor=2.0, mode="nearest"), (cout, cin, 3, 3),
                                           dy.double(), padding=1)
         assert ops.wgrad16_supported(cin, 0, cout, h, w, 3, 1, True)
-        try:
-            _lib.check(_lib.load().dsg_set_tuning(39, 0))
+        with ops.tuning(wgrad16_fold=0):
             ops.conv_wgrad(xb, dyb, dw, ksize=3, upsample=True, dy_sums=sums)
-        finally:
-            _lib.load().dsg_set_tuning(39, 1)
         ops.conv_wgrad(ops.upsample_nearest2x(xb), dyb, old, ksize=3, dy_sums=sums_old)
         # the folded form: the same sums in another order
         fdw = torch.full((cout, cin, 3, 3), 0.5, dtype=torch.float32, device=DEV)
@@ -129,10 +125,9 @@ def test_wgrad16_sampler_convs_read_the_half_resolution_operand_in_place(case, m
 @pytest.mark.parametrize("shape", [(128, 64, 128, 16, 32, 3), (64, 0, 256, 12, 64, 5), (384, 0, 128, 32, 32, 4)],
                          ids=["concat_192_128", "64_256_two_strips", "384_128"])
 def test_wgrad16_wide_workgroups_match_the_64x64_ones(shape, act):
-    """cout % 128 == 0 selects 64 ci x 128 co workgroups (a wave keeps two co tiles, one workgroup per CU; dsg_set_tuning
-    key 29): the same products in the same order per run, other runs of pixels per partial slab -- equal to fp32 round-off
+    """cout % 128 == 0 selects 64 ci x 128 co workgroups (a wave keeps two co tiles, one workgroup per CU; the
+    wgrad16_wide switch): the same products in the same order per run, other runs of pixels per partial slab -- equal to fp32 round-off
     of the slab sum, and the dY sums likewise."""
-    from drivescenegen_amd import _lib
     c0, c1, cout, h, w, n = shape
     cin = c0 + c1
     b0 = ops.to_blocked(_t(21, (n, c0, h, w)).to(DEV), "bf16")
@@ -142,16 +137,13 @@ def test_wgrad16_wide_workgroups_match_the_64x64_ones(shape, act):
     if act != "plain":
         ss = torch.stack([1 + _t(24, (n, cin), 0.1), _t(25, (n, cin), 0.1)], -1).contiguous().to(DEV)
     res = []
-    try:
-        for wide in (0, 1):
-            _lib.check(_lib.load().dsg_set_tuning(29, wide))
+    for wide in (0, 1):
+        with ops.tuning(wgrad16_wide=wide):
             dw = torch.zeros((cout, cin, 3, 3), dtype=torch.float32, device=DEV)
             sums = torch.zeros((n, cout), dtype=torch.float32, device=DEV)
             bg = torch.zeros(cout, dtype=torch.float32, device=DEV)
             ops.conv_wgrad(b0, dy, dw, src1=b1, ksize=3, gn_scale_shift=ss, silu=act == "gn_silu", dy_sums=sums, bias_grad=bg)
             res.append((dw, sums, bg))
-    finally:
-        _lib.load().dsg_set_tuning(29, 1)
     for a, b in zip(*res):
         assert torch.isfinite(b).all()
         assert float((a - b).abs().max()) <= 2e-6 * float(a.abs().max()), float((a - b).abs().max())
@@ -308,26 +300,22 @@ def test_upsampler_data_gradient_routes_agree(cfg, mode, monkeypatch):
 
 
 def test_folded_upsampler_weight_gradient_in_a_whole_step():
-    """dsg_set_tuning key 39 on / off on a whole bf16 training step of the tiny network (its up-sampler conv -- 64 -> 64 channels
+    """The wgrad16_fold switch on / off on a whole bf16 training step of the tiny network (its up-sampler conv -- 64 -> 64 channels
     on a 32 x 32 map -- takes the folded kernel): same forward, every gradient within fp32 round-off of the other form (the
     two forms add the same bf16 products in another order)."""
-    from drivescenegen_amd import _lib
     cfg = CFG1
     b, ss = 2, cfg["sample_size"]
     x0 = torch.from_numpy(synth.synth_scene_rasters(b, cfg["in_channels"], ss, ss, 5))
     noise = torch.from_numpy(synth.normal(6, tuple(x0.shape)))
     t = torch.tensor([12, 700])
     res = []
-    try:
-        for fold in (1, 0):
-            _lib.check(_lib.load().dsg_set_tuning(39, fold))
+    for fold in (1, 0):
+        with ops.tuning(wgrad16_fold=fold):
             net = synth_weights(d.UNet2DModel(**cfg)).to(DEV).train().set_compute_dtype("bf16")
             noisy = d.DDPMScheduler().add_noise(x0.to(DEV), noise.to(DEV), t.to(DEV))
             loss = d.mse_loss(net(noisy, t.to(DEV), return_dict=False)[0], noise.to(DEV))
             loss.backward()
             res.append((float(loss.detach().cpu()), {k: p.grad.detach().cpu().double() for k, p in net.named_parameters()}))
-    finally:
-        _lib.load().dsg_set_tuning(39, 1)
     assert res[0][0] == res[1][0]
     ups = [k for k in res[0][1] if k.endswith("upsamplers.0.conv.weight")]
     assert ups

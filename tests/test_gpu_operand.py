@@ -10,7 +10,7 @@ once by a streaming pass and the kernel DMAs its patches straight into LDS.  Che
     including the GroupNorm statistics it leaves;
 (c) the image path against fp64 to the split path's fp32-class bound;
 (d) calls that cannot take an image refuse it; the query's pays-off rule;
-(e) the whole network with and without it (dsg_set_tuning key 26): bitwise."""
+(e) the whole network with and without it (ops.tuning(pre=0)): bitwise."""
 import numpy as np
 import pytest
 import torch
@@ -19,7 +19,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import drivescenegen_amd as d  # noqa: E402
-from drivescenegen_amd import _lib, ops, synth  # noqa: E402
+from drivescenegen_amd import ops, synth  # noqa: E402
 from tests.common import CFG2, noisy_inputs, rel_l2, synth_weights  # noqa: E402
 
 DEV = "cuda"
@@ -28,11 +28,9 @@ DEV = "cuda"
 @pytest.fixture(autouse=True)
 def every_qualifying_conv_gets_an_image():
     """The launcher's default pays-off threshold (16 stagings per patch: the folded up-samplers) would leave the resnet convs
-    on their own staging; the tests lower it to 4 (dsg_set_tuning key 27) so that every form of the PRE kernel runs."""
-    lib = _lib.load()
-    _lib.check(lib.dsg_set_tuning(27, 4))
-    yield
-    _lib.check(lib.dsg_set_tuning(27, 16))
+    on their own staging; the tests lower it to 4 (the pre_min_ct switch) so that every form of the PRE kernel runs."""
+    with ops.tuning(pre_min_ct=4):
+        yield
 
 
 def _t(seed, shape, scale=1.0):
@@ -172,15 +170,11 @@ def test_calls_that_stage_their_own_patch_refuse_an_image():
 
 
 def test_whole_network_with_and_without_operand_images_is_bitwise():
-    lib = _lib.load()
     net = synth_weights(d.UNet2DModel(**CFG2)).to(DEV).eval().requires_grad_(False)
     x = noisy_inputs(CFG2, 16).to(DEV)
     t = torch.full((16,), 500, dtype=torch.int64, device=DEV)
     y1 = net(x, t).sample.clone()
-    _lib.check(lib.dsg_set_tuning(26, 0))
-    try:
+    with ops.tuning(pre=0):
         y0 = net(x, t).sample.clone()
-    finally:
-        _lib.check(lib.dsg_set_tuning(26, 1))
     assert torch.isfinite(y1).all()
     assert torch.equal(y0, y1), float((y0 - y1).abs().max())

@@ -9,7 +9,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from drivescenegen_amd import _lib, ops, synth  # noqa: E402
+from drivescenegen_amd import ops, synth  # noqa: E402
 from oracle.scheduler_oracle import OracleDDIMScheduler, OracleDDPMScheduler  # noqa: E402
 from oracle.unet_oracle import timestep_embedding  # noqa: E402
 from tests.common import max_abs, rel_l2  # noqa: E402
@@ -323,19 +323,13 @@ def test_conv_f32_kernels_take_blocked_layouts(case):
                                    src_blocked=sb, dst_blocked=db, **kw)
     if "conv_in" in name or "conv_out" in name:
         # image -> blocked and blocked -> image calls now have kernels of their own (csrc/conv_in.hip, conv_out.hip;
-        # tests/test_gpu_conv_in.py, test_gpu_conv_out.py): same values to round-off; with them switched off (tuning keys
-        # 21 / 22) the f32 / VALU kernels serve the calls as before, bit for bit
+        # tests/test_gpu_conv_in.py, test_gpu_conv_out.py): same values to round-off; with them switched off (the conv_in /
+        # conv_out switches) the f32 / VALU kernels serve the calls as before, bit for bit
         near = run()
         near = ops.from_blocked(near) if db else near
         assert float((near - want).abs().max()) <= 3e-6 * float(want.abs().max())
-        lib = _lib.load()
-        _lib.check(lib.dsg_set_tuning(21, 0))
-        _lib.check(lib.dsg_set_tuning(22, 0))
-        try:
+        with ops.tuning(conv_in=0, conv_out=0):
             got = run()
-        finally:
-            _lib.check(lib.dsg_set_tuning(21, 1))
-            _lib.check(lib.dsg_set_tuning(22, 1))
     else:
         got = run()
     got = ops.from_blocked(got) if db else got
@@ -345,10 +339,9 @@ def test_conv_f32_kernels_take_blocked_layouts(case):
 @pytest.mark.parametrize("case", [c for c in H2_CASES if (len(c) <= 10 or c[10] == 3) and not c[6] and c[1] + c[2] <= 128
                                   and c[5] % 32 == 0], ids=lambda c: c[0])
 def test_conv_h2_small_workgroup_geometry_is_bit_identical(case):
-    """The shallow levels' geometry (32 couts x 8 rows per workgroup, two workgroups per CU; dsg_set_tuning key 16):
+    """The shallow levels' geometry (32 couts x 8 rows per workgroup, two workgroups per CU; the bm32 switch):
     the same contraction order per output, so results and epilogue statistics equal the 64 x 16 geometry's bit for
     bit."""
-    from drivescenegen_amd import _lib
     name, c0, c1, cout, h, w, ups, gn, temb, res = case[:10]
     batch, cin = 2, c0 + c1
     d = lambda t: None if t is None else t.to(DEV)
@@ -364,14 +357,10 @@ def test_conv_h2_small_workgroup_geometry_is_bit_identical(case):
     kw = dict(src1=b(x1), ksize=3, gn_scale_shift=ss, silu=gn, temb=tp[:, 3:] if temb else None,
               temb_stride=tp.stride(0), residual=b(r), cout=cout, weight_h2=wh, src_blocked=True, dst_blocked=True,
               want_stats=True)
-    lib = _lib.load()
-    try:
-        _lib.check(lib.dsg_set_tuning(16, 0))
+    with ops.tuning(bm32=0):
         want, wstats = ops.conv2d_fused(b(x0), wr, bias, **kw)
-        _lib.check(lib.dsg_set_tuning(16, 2))  # (2: take the small geometry whatever the grid size)
+    with ops.tuning(bm32=2):  # (2: take the small geometry whatever the grid size)
         got, gstats = ops.conv2d_fused(b(x0), wr, bias, **kw)
-    finally:
-        lib.dsg_set_tuning(16, 0)
     assert torch.equal(got, want), float((got - want).abs().max())
     assert torch.equal(gstats, wstats)
 
@@ -408,10 +397,9 @@ def test_conv_h2_stride2_space_to_depth(c, cout, h, w):
 def test_narrow_maps_take_splitk_fold_and_stride2_kernels(mode, c, cout, h, w, batch):
     """Maps narrower than the 32-column tile (BASELINE configs[3]: 512 channels at 16 x 16, the up-sampler out of it and the
     down-sampler into it) on the kernels the wide maps use -- split-K slices + reduce pass, the folded up-sampler, the stride-2
-    space-to-depth kernel (dsg_set_tuning key 32; before round 4: one-slice / exact f32-MFMA kernels).  Against fp64 in the
-    split convs' round-off class, against the key-32-off call of the same arguments (fp32 round-off: another summation order),
+    space-to-depth kernel (the narrow switch; before round 4: one-slice / exact f32-MFMA kernels).  Against fp64 in the
+    split convs' round-off class, against the narrow=0 call of the same arguments (fp32 round-off: another summation order),
     and the epilogue statistics of what was written."""
-    from drivescenegen_amd import _lib
     d = lambda t: None if t is None else t.to(DEV)
     x = _t(61, (batch, c, h, w), 1.2)
     wt = _t(62, (cout, c, 3, 3), 1.0 / np.sqrt(9 * c))
@@ -436,15 +424,11 @@ def test_narrow_maps_take_splitk_fold_and_stride2_kernels(mode, c, cout, h, w, b
         want = F.conv2d(x.double(), wt.double(), bias.double(), stride=2, padding=1)
         mag = F.conv2d(x.double().abs(), wt.double().abs(), None, stride=2, padding=1) + 1e-30
         kw.update(stride=2, weight_h2_s2=ops.relayout_conv_weight_h2_s2(d(wt)))
-    lib = _lib.load()
     got = {}
-    try:
-        for on in (0, 1):
-            _lib.check(lib.dsg_set_tuning(32, on))
+    for on in (0, 1):
+        with ops.tuning(narrow=on):
             y, st = ops.conv2d_fused(xb, wr, d(bias), **kw)
             got[on] = (ops.from_blocked(y).cpu(), st)
-    finally:
-        lib.dsg_set_tuning(32, 1)
     assert not torch.equal(got[0][0], got[1][0])   # (another kernel really ran)
     for on in (0, 1):
         err = float(((got[on][0].double() - want).abs() / mag).max())
@@ -643,11 +627,9 @@ def test_conv_split_path_random_shapes(case):
 
 @pytest.mark.parametrize("cin,cout,res,gn", [(64, 64, True, True), (128, 64, False, True), (128, 128, True, True), (64, 128, False, False)])
 def test_conv_two_workgroups_per_cu_is_bit_identical(cin, cout, res, gn):
-    """The one-weight-slab kernel (8-row tiles, two workgroups per CU: dsg_set_tuning key 20) serves the cin <= 128 convs of
+    """The one-weight-slab kernel (8-row tiles, two workgroups per CU: the ws2 switch) serves the cin <= 128 convs of
     grids with >= 512 workgroups.  Same K order, same summation tree of the statistics: its results and its per-tile
     GroupNorm partials are BITWISE those of the 16-row kernel."""
-    from drivescenegen_amd import _lib
-    lib = _lib.load()
     n, h, w = 4, 128, 128   # 4 x 16 x 4 x (cout / 64) 8-row tiles >= 512 for cout 128; cout 64: n = 8
     if cout == 64:
         n = 8
@@ -659,14 +641,11 @@ def test_conv_two_workgroups_per_cu_is_bit_identical(cin, cout, res, gn):
     ss = d(_t(25, (n, cin, 2))) if gn else None
     wr, wh = ops.relayout_conv_weight(wt), ops.relayout_conv_weight_h2(wt)
     outs = []
-    try:
-        for on in (0, 1):
-            _lib.check(lib.dsg_set_tuning(20, on))
+    for on in (0, 1):
+        with ops.tuning(ws2=on):
             y, st = ops.conv2d_fused(x, wr, bias, residual=r, gn_scale_shift=ss, silu=gn, weight_h2=wh, want_stats=True,
                                      src_blocked=True, dst_blocked=True)
             outs.append((y.clone(), st.clone()))
-    finally:
-        lib.dsg_set_tuning(20, 1)
     assert torch.equal(outs[0][0], outs[1][0])
     assert torch.equal(outs[0][1], outs[1][1])
     ref = F.conv2d(F.silu(ops.from_blocked(x).cpu().double() * ss.cpu().double()[:, :, 0, None, None] + ss.cpu().double()[:, :, 1, None, None])

@@ -147,9 +147,8 @@ def test_attention_backward_bf16_matrix_cores(n, c, heads, l, mode):
 def test_attention_backward_fp32_on_the_matrix_cores_is_in_the_valu_kernels_class(n, c, heads, l, mag):
     """Round 6: `dsg_attention_bwd` (the fp32 tape; training_pipeline.py:86 through the mid block's Attention) runs head_dim 8 on the
     matrix cores with every product as an fp16x2 split (three MFMAs, dO scaled to [1, 2) by a power of two first) instead of the
-    two VALU kernels.  Against torch autograd in fp64, next to the VALU kernels (tuning key 38 = 0) on the same inputs: the same
+    two VALU kernels.  Against torch autograd in fp64, next to the VALU kernels (att_bwd_split = 0) on the same inputs: the same
     error class -- also for gradients of 1e-6 (no loss scale) and of 30 (a large one)."""
-    from drivescenegen_amd import _lib
     qkv = _t(31, (n, 3 * c, l), 1.2).double().requires_grad_(True)
     dd = c // heads
     q, k, v = [qkv[:, i * c:(i + 1) * c].view(n, heads, dd, l).transpose(2, 3) for i in range(3)]
@@ -158,14 +157,10 @@ def test_attention_backward_fp32_on_the_matrix_cores_is_in_the_valu_kernels_clas
     o.backward(do.double())
     ref = qkv.grad
     out, lse = ops.attention_train(qkv.detach().float().to(DEV), heads)
-    lib = _lib.load()
     got = {}
-    try:
-        for on in (1, 0):
-            _lib.check(lib.dsg_set_tuning(38, on))
+    for on in (1, 0):
+        with ops.tuning(att_bwd_split=on):
             got[on] = ops.attention_bwd(qkv.detach().float().to(DEV), out, do.to(DEV), lse, heads).cpu().double()
-    finally:
-        lib.dsg_set_tuning(38, 1)
     assert not torch.equal(got[0], got[1])            # (another kernel really ran)
     for i, name in enumerate(("dq", "dk", "dv")):
         b = ref[:, i * c:(i + 1) * c]
@@ -287,11 +282,10 @@ def test_wgrad_split_path_random_shapes(case):
                          ids=lambda c: "c%d+%d_o%d_%dx%d" % c[:5])
 def test_wgrad_wide_workgroups_match_the_32x64_ones(case):
     """cout % 128 == 0 selects the 32 ci x 128 co workgroup of the fp32-equivalent 3x3 weight gradient (conv_wgrad_h2w_kernel:
-    two co tiles per wave, the centre tap's unit on pinned registers; dsg_set_tuning key 31 = 0 keeps the 32 x 64 workgroup).
+    two co tiles per wave, the centre tap's unit on pinned registers; wgrad_h2_wide = 0 keeps the 32 x 64 workgroup).
     Both against fp64 autograd (3e-5 class, as the random-shape test) and against each other: per (ci, co, tap) the products are
     summed over a run's pixels in the same order, runs are cut by the (smaller) pair count, so the two agree to the rounding of
     the split-K reduce (1e-6), and the dY-sum by-products likewise."""
-    from drivescenegen_amd import _lib
     c0, c1, cout, h, w, gn, batch = case
     cin = c0 + c1
     x0 = _t(71, (batch, c0, h, w))
@@ -304,16 +298,12 @@ def test_wgrad_wide_workgroups_match_the_32x64_ones(case):
     d = lambda t: None if t is None else t.to(DEV)
     ss = ops.gn_scale_shift(d(x0), d(gamma), d(beta), 8, 1e-5, src1=d(x1)) if gn else None
     got = {}
-    lib = _lib.load()
-    try:
-        for wide in (0, 1):
-            _lib.check(lib.dsg_set_tuning(31, wide))
+    for wide in (0, 1):
+        with ops.tuning(wgrad_h2_wide=wide):
             dw = torch.zeros((cout, cin, 3, 3), device=DEV)
             sums = torch.zeros((batch, cout), device=DEV)
             ops.conv_wgrad(d(x0), d(dy), dw, src1=d(x1), ksize=3, gn_scale_shift=ss, silu=gn, dy_sums=sums, dy_sums_stride=cout)
             got[wide] = (dw.cpu(), sums.cpu())
-    finally:
-        lib.dsg_set_tuning(31, 1)
     for wide in (0, 1):
         _close(got[wide][0], want.float(), rel=3e-5, ab=3e-5)
     scale = float(want.abs().max())

@@ -137,10 +137,9 @@ S2_CASES = [("tile32_16rows", 64, 64, 32, 64, 2), ("cin128_cout64_big", 128, 64,
 def test_stride2_conv_fp32_nchw_on_the_space_to_depth_kernel(case, scale):
     """Downsample2D's conv (3x3, stride 2, padding 1; diffusers Downsample2D inside the down blocks of
     DriveSceneGen/utils/model/unet_2d.py's network) on fp32 [N,C,H,W] tensors -- the fp32 training tape's layout -- through the
-    2x2-tap kernel over the space-to-depth image (dsg_set_tuning key 40; the channel-blocked form has served the inference plan
+    2x2-tap kernel over the space-to-depth image (the s2_nchw switch; the channel-blocked form has served the inference plan
     since round 2): against F.conv2d in fp64, against the exact f32 kernel it replaces, statistics and range guard included
     (scale 3e5: the source is outside fp16's range and goes through the per-image power-of-two pre-scaling)."""
-    from drivescenegen_amd import _lib
     name, cin, cout, h, w, n = case
     x = _t(11, (n, cin, h, w), scale)
     wt = _t(12, (cout, cin, 3, 3), 1.0 / np.sqrt(9 * cin))
@@ -158,11 +157,8 @@ def test_stride2_conv_fp32_nchw_on_the_space_to_depth_kernel(case, scale):
     s_got = stats.cpu().sum(2)
     assert torch.allclose(s_got[..., 0], ref.sum((2, 3)), rtol=1e-5, atol=1e-4 * scale * scale)
     assert torch.allclose(s_got[..., 1], ref.pow(2).sum((2, 3)), rtol=1e-5)
-    try:   # the exact kernel (needs the fp32 engine layout; no statistics from it)
-        _lib.check(_lib.load().dsg_set_tuning(40, 0))
+    with ops.tuning(s2_nchw=0):   # the exact kernel (needs the fp32 engine layout; no statistics from it)
         with pytest.raises(RuntimeError):
             ops.conv2d_fused(xd, None, bias.to(DEV), **kw)
         old = ops.conv2d_fused(xd, ops.relayout_conv_weight(wt.to(DEV)), bias.to(DEV), ksize=3, stride=2, cout=cout, residual=res.to(DEV))
-    finally:
-        _lib.load().dsg_set_tuning(40, 1)
     assert rel_l2(got.cpu(), old.cpu()) <= 3e-6
