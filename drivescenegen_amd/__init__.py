@@ -5,7 +5,7 @@ pipeline/training_pipeline.py} import from diffusers: same names, arguments, sta
 checkpoint folder; all arithmetic runs in hand-written HIP kernels behind the C ABI of include/dsg.h.
 """
 from .unet import UNet2DModel  # noqa: F401
-from .schedulers import DDPMScheduler, DDIMScheduler, RePaintScheduler  # noqa: F401
+from .schedulers import DDPMScheduler, DDIMScheduler, DPMSolverMultistepScheduler, RePaintScheduler  # noqa: F401
 from .pipelines import DDPMPipeline, DDIMPipeline, RePaintPipeline, ImagePipelineOutput  # noqa: F401
 from .optimization import get_cosine_schedule_with_warmup  # noqa: F401
 from .train_loop import fit, notebook_launcher, sample_to_pil  # noqa: F401

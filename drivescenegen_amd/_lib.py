@@ -92,6 +92,18 @@ class RepaintStepArgs(C.Structure):
     ]
 
 
+class DpmSolverStepArgs(C.Structure):
+    """Mirror of ``dsg_dpmsolver_step_args`` (include/dsg.h)."""
+    _fields_ = [
+        ("sample", C.c_void_p), ("eps", C.c_void_p), ("m1", C.c_void_p), ("m2", C.c_void_p), ("noise", C.c_void_p),
+        ("prev", C.c_void_p), ("m0_out", C.c_void_p), ("noise_out", C.c_void_p),
+        ("numel", C.c_int64), ("order", C.c_int32), ("add_noise", C.c_int32),
+        ("sigma_s", C.c_float), ("alpha_s", C.c_float), ("inv_r0", C.c_float), ("inv_r1", C.c_float), ("q", C.c_float),
+        ("p", C.c_float), ("kx", C.c_float), ("c0", C.c_float), ("c1", C.c_float), ("c2", C.c_float), ("cn", C.c_float),
+        ("seed", C.c_uint64), ("offset", C.c_uint64),
+    ]
+
+
 class UNetConfig(C.Structure):
     """Mirror of ``dsg_unet_config`` (include/dsg.h)."""
     _fields_ = [
@@ -182,6 +194,7 @@ SIGNATURES = {
     "dsg_ddim_step": [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp],
     "dsg_repaint_step": [C.POINTER(RepaintStepArgs), _vp],
     "dsg_repaint_undo": [_vp, _vp, _vp, _i64, _f32, _f32, C.c_uint64, C.c_uint64, _vp],
+    "dsg_dpmsolver_step": [C.POINTER(DpmSolverStepArgs), _vp],
     "dsg_postprocess": [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "dsg_unet_create": [C.POINTER(UNetConfig), C.POINTER(_vp)],
     "dsg_unet_set_param": [_vp, C.c_char_p, _vp, _i64, _vp],

@@ -277,6 +277,85 @@ __global__ __launch_bounds__(256) void repaint_undo_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// DPM-Solver++ multistep (Lu et al., 2022; diffusers' DPMSolverMultistepScheduler.step): the data-prediction form of the
+// diffusion ODE's exponential integrator, orders 1-3, and its SDE variant.  One pass per step, per element and in THIS order
+// (include/dsg.h states it as the contract):
+//   m0   = (x - sigma_s*e) / alpha_s                      -> m0_out (the history entry this step adds)
+//   D10  = inv_r0*(m0 - m1)                               ORDER >= 2
+//   D11  = inv_r1*(m1 - m2);  dd = D10 - D11;  D1 = D10 + q*dd;  D2 = p*dd        ORDER == 3 (D1 = D10 at order 2)
+//   prev = kx*x + c0*m0  [+ c1*D1]  [+ c2*D2]  [+ cn*z]   summed left to right
+// The host passes signed coefficients.  z as in repaint_step_kernel (NOISE 1: read from `nz`, 2: this lane's Philox block;
+// 0: no noise term).  VEC: every pointer is 16-byte aligned, so a lane's 4 elements are one dwordx4 access per stream; the last
+// numel % 4 elements take the per-element path, as everything does without VEC.
+struct dpm_coef {
+  float sigma_s, alpha_s, inv_r0, inv_r1, q, p, kx, c0, c1, c2, cn;
+};
+
+template <int ORDER, bool NOISE>
+__device__ __forceinline__ void dpm_elem(float x, float e, float m1, float m2, float z, const dpm_coef& k, float& prev,
+                                         float& m0o) {
+  const float m0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(k.sigma_s, e)), k.alpha_s);
+  float r = __fadd_rn(__fmul_rn(k.kx, x), __fmul_rn(k.c0, m0));
+  if (ORDER >= 2) {
+    const float d10 = __fmul_rn(k.inv_r0, __fsub_rn(m0, m1));
+    float d1 = d10;
+    if (ORDER == 3) {
+      const float d11 = __fmul_rn(k.inv_r1, __fsub_rn(m1, m2));
+      const float dd = __fsub_rn(d10, d11);
+      d1 = __fadd_rn(d10, __fmul_rn(k.q, dd));
+      r = __fadd_rn(r, __fmul_rn(k.c1, d1));
+      r = __fadd_rn(r, __fmul_rn(k.c2, __fmul_rn(k.p, dd)));
+    } else {
+      r = __fadd_rn(r, __fmul_rn(k.c1, d1));
+    }
+  }
+  if (NOISE) r = __fadd_rn(r, __fmul_rn(k.cn, z));
+  prev = r;
+  m0o = m0;
+}
+
+template <int ORDER, int NOISE, bool VEC>
+__global__ __launch_bounds__(256) void dpmsolver_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                             const float* __restrict__ m1, const float* __restrict__ m2,
+                                                             const float* __restrict__ nz, float* __restrict__ prev,
+                                                             float* __restrict__ m0_out, float* __restrict__ noise_out,
+                                                             int64_t numel, dpm_coef k, uint32_t seed_lo, uint32_t seed_hi,
+                                                             uint32_t off_lo, uint32_t off_hi) {
+  const int64_t blocks = (numel + 3) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < blocks; c += stride) {
+    const int64_t e = c << 2;
+    const bool vec = VEC && e + 4 <= numel;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (NOISE == 1) repaint_noise4<0>(nz, c, numel, vec, seed_lo, seed_hi, off_lo, off_hi, z);
+    if (NOISE == 2) repaint_noise4<1>(nz, c, numel, vec, seed_lo, seed_hi, off_lo, off_hi, z);
+    if (vec) {
+      const float4 xv = *reinterpret_cast<const float4*>(x + e);
+      const float4 ev = *reinterpret_cast<const float4*>(eps + e);
+      float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av, r, m;
+      if (ORDER >= 2) av = *reinterpret_cast<const float4*>(m1 + e);
+      if (ORDER == 3) bv = *reinterpret_cast<const float4*>(m2 + e);
+      dpm_elem<ORDER, NOISE != 0>(xv.x, ev.x, av.x, bv.x, z[0], k, r.x, m.x);
+      dpm_elem<ORDER, NOISE != 0>(xv.y, ev.y, av.y, bv.y, z[1], k, r.y, m.y);
+      dpm_elem<ORDER, NOISE != 0>(xv.z, ev.z, av.z, bv.z, z[2], k, r.z, m.z);
+      dpm_elem<ORDER, NOISE != 0>(xv.w, ev.w, av.w, bv.w, z[3], k, r.w, m.w);
+      *reinterpret_cast<float4*>(prev + e) = r;
+      *reinterpret_cast<float4*>(m0_out + e) = m;
+      if (NOISE != 0 && noise_out) *reinterpret_cast<float4*>(noise_out + e) = make_float4(z[0], z[1], z[2], z[3]);
+    } else {
+      for (int j = 0; j < 4 && e + j < numel; ++j) {
+        const int64_t i = e + j;
+        float r, m;
+        dpm_elem<ORDER, NOISE != 0>(x[i], eps[i], ORDER >= 2 ? m1[i] : 0.f, ORDER == 3 ? m2[i] : 0.f, z[j], k, r, m);
+        prev[i] = r;
+        m0_out[i] = m;
+        if (NOISE != 0 && noise_out) noise_out[i] = z[j];
+      }
+    }
+  }
+}
+
 // (x/2 + 0.5).clamp(0,1), NCHW -> NHWC.  grid = (ceil(hw/256), n)
 template <int MODE>
 __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restrict__ x, void* __restrict__ out, int c,
@@ -449,6 +528,69 @@ DSG_API int dsg_repaint_undo(const float* sample, const float* noise, float* out
     if (vec) DSG_UNDO_LAUNCH(1, true); else DSG_UNDO_LAUNCH(1, false);
   }
 #undef DSG_UNDO_LAUNCH
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
+
+namespace dsg {
+// do [a, a + bytes) and [b, b + bytes) share a byte?  (NULL overlaps nothing)
+static inline bool overlaps(const void* a, const void* b, uint64_t bytes) {
+  if (!a || !b) return false;
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y ? y - x < bytes : x - y < bytes;
+}
+
+template <int ORDER, int NOISE>
+static void dpmsolver_launch(const dsg_dpmsolver_step_args* a, bool vec, const float* nz, hipStream_t st) {
+  const dpm_coef k = {a->sigma_s, a->alpha_s, a->inv_r0, a->inv_r1, a->q, a->p, a->kx, a->c0, a->c1, a->c2, a->cn};
+  const dim3 grid(philox_blocks(a->numel)), block(256);
+  const uint32_t s0 = (uint32_t)a->seed, s1 = (uint32_t)(a->seed >> 32), o0 = (uint32_t)a->offset, o1 = (uint32_t)(a->offset >> 32);
+  if (vec)
+    hipLaunchKernelGGL((dpmsolver_step_kernel<ORDER, NOISE, true>), grid, block, 0, st, a->sample, a->eps, a->m1, a->m2, nz,
+                       a->prev, a->m0_out, a->noise_out, a->numel, k, s0, s1, o0, o1);
+  else
+    hipLaunchKernelGGL((dpmsolver_step_kernel<ORDER, NOISE, false>), grid, block, 0, st, a->sample, a->eps, a->m1, a->m2, nz,
+                       a->prev, a->m0_out, a->noise_out, a->numel, k, s0, s1, o0, o1);
+}
+
+template <int ORDER>
+static void dpmsolver_launch_order(const dsg_dpmsolver_step_args* a, bool vec, hipStream_t st) {
+  if (!a->add_noise) dpmsolver_launch<ORDER, 0>(a, vec, nullptr, st);
+  else if (a->noise) dpmsolver_launch<ORDER, 1>(a, vec, a->noise, st);
+  else dpmsolver_launch<ORDER, 2>(a, vec, nullptr, st);
+}
+}  // namespace dsg
+
+DSG_API int dsg_dpmsolver_step(const dsg_dpmsolver_step_args* a, void* stream) {
+  DSG_CHECK_ARG(a, "dsg_dpmsolver_step: NULL args");
+  DSG_CHECK_ARG(a->sample && a->eps && a->prev && a->m0_out, "dsg_dpmsolver_step: NULL pointer");
+  DSG_CHECK_ARG(a->numel > 0, "dsg_dpmsolver_step: numel must be positive");
+  DSG_CHECK_ARG(a->order >= 1 && a->order <= 3, "dsg_dpmsolver_step: order=%d is not 1, 2 or 3", a->order);
+  DSG_CHECK_ARG(a->order < 2 || a->m1, "dsg_dpmsolver_step: order %d needs the history entry m1", a->order);
+  DSG_CHECK_ARG(a->order < 3 || a->m2, "dsg_dpmsolver_step: order %d needs the history entry m2", a->order);
+  // what THIS call reads and writes (a history entry above the order, or a noise pointer without add_noise, is not touched)
+  const float* m1 = a->order >= 2 ? a->m1 : nullptr;
+  const float* m2 = a->order >= 3 ? a->m2 : nullptr;
+  const float* nz = a->add_noise ? a->noise : nullptr;
+  float* nout = a->add_noise ? a->noise_out : nullptr;
+  const uint64_t bytes = (uint64_t)a->numel * sizeof(float);
+  const void* ins[5] = {a->sample, a->eps, m1, m2, nz};
+  const void* outs[3] = {a->prev, a->m0_out, nout};
+  for (int o = 0; o < 3; ++o) {
+    for (int i = 0; i < 5; ++i)
+      DSG_CHECK_ARG(!dsg::overlaps(outs[o], ins[i], bytes), "dsg_dpmsolver_step: an output overlaps an input (output %d, input %d)",
+                    o, i);
+    for (int p = o + 1; p < 3; ++p)
+      DSG_CHECK_ARG(!dsg::overlaps(outs[o], outs[p], bytes), "dsg_dpmsolver_step: two outputs overlap (%d, %d)", o, p);
+  }
+  const bool vec = dsg::aligned16(a->sample) && dsg::aligned16(a->eps) && dsg::aligned16(m1) && dsg::aligned16(m2) &&
+                   dsg::aligned16(nz) && dsg::aligned16(a->prev) && dsg::aligned16(a->m0_out) && dsg::aligned16(nout);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  dsg_dpmsolver_step_args b = *a;     // the kernels get exactly the pointers checked above
+  b.m1 = m1; b.m2 = m2; b.noise = nz; b.noise_out = nout;
+  if (a->order == 1) dsg::dpmsolver_launch_order<1>(&b, vec, st);
+  else if (a->order == 2) dsg::dpmsolver_launch_order<2>(&b, vec, st);
+  else dsg::dpmsolver_launch_order<3>(&b, vec, st);
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }

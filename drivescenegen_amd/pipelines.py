@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .schedulers import DDIMScheduler, DDPMScheduler, RePaintScheduler, _randn_like_reference
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, RePaintScheduler, _randn_like_reference
 from .unet import UNet2DModel
 
 
@@ -48,6 +48,7 @@ def numpy_to_pil(images: np.ndarray):
 class _PipelineBase:
     _class_name = "DDPMPipeline"
     _scheduler_cls = DDPMScheduler
+    _kept_scheduler_classes = ()    # scheduler classes a saved folder may name that this pipeline runs as they are
 
     def __init__(self, unet, scheduler):
         self.unet = unet
@@ -80,10 +81,11 @@ class _PipelineBase:
             index = json.load(f)
         sched_name = index.get("scheduler", ["diffusers", "DDPMScheduler"])[1]
         sched_cls = {"DDPMScheduler": DDPMScheduler, "DDIMScheduler": DDIMScheduler,
-                     "RePaintScheduler": RePaintScheduler}.get(sched_name)
+                     "RePaintScheduler": RePaintScheduler,
+                     "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler}.get(sched_name)
         if sched_cls is None:
             raise NotImplementedError(f"scheduler class {sched_name!r} not supported")
-        if cls._scheduler_cls is not sched_cls:
+        if cls._scheduler_cls is not sched_cls and sched_cls not in cls._kept_scheduler_classes:
             # diffusers lets a pipeline adopt a compatible scheduler config
             scheduler = cls._scheduler_cls.from_config(
                 {k: v for k, v in json.load(open(os.path.join(path, "scheduler", "scheduler_config.json"))).items()})
@@ -231,9 +233,14 @@ def _device_timestep_rows(timesteps, batch, device):
     return timesteps.to(device=device, dtype=torch.long)[:, None].expand(-1, batch).contiguous()
 
 
+def _is_dpmsolver(scheduler):
+    return isinstance(scheduler, DPMSolverMultistepScheduler)
+
+
 class DDPMPipeline(_PipelineBase):
     _class_name = "DDPMPipeline"
     _scheduler_cls = DDPMScheduler
+    _kept_scheduler_classes = (DPMSolverMultistepScheduler,)
 
     @torch.no_grad()
     def __call__(self, batch_size: int = 1, generator=None, num_inference_steps: int = 1000, output_type="pil",
@@ -249,13 +256,23 @@ class DDPMPipeline(_PipelineBase):
             # tensors and keeps its rows so that N-GPU output == 1-GPU output
             self.scheduler.set_timesteps(num_inference_steps)
             ts = [int(t) for t in self.scheduler.timesteps]
-            stream = _NoiseStream(full, generator, self.device, rows, count=1 + sum(1 for t in ts if t > 0))
+            if _is_dpmsolver(self.scheduler):
+                # the ODE solver takes no noise at all; its SDE variant one tensor per step, the last included -- from this
+                # stream, unless the scheduler makes its own in the step kernel (use_device_noise)
+                sch = self.scheduler
+                if sch.needs_step_noise and sch.noise_mode == "device" and shard is not None:
+                    raise NotImplementedError("DDPMPipeline: shard= with the SDE solver's device noise (every rank would "
+                                              "generate the same tensor for different rows)")
+                draws = [sch.needs_step_noise and sch.noise_mode != "device"] * len(ts)
+            else:
+                draws = [t > 0 for t in ts]
+            stream = _NoiseStream(full, generator, self.device, rows, count=1 + sum(draws))
             try:
                 image = stream.draw()
                 tdev = _device_timestep_rows(self.scheduler.timesteps, image.shape[0], self.device)
                 for i, t in enumerate(ts):
                     eps = self.unet(image, tdev[i]).sample
-                    noise = stream.draw() if t > 0 else None     # (drawn while the previous step was enqueued; PCIe under the forward)
+                    noise = stream.draw() if draws[i] else None  # (drawn while the previous step was enqueued; PCIe under the forward)
                     image = self.scheduler.step(eps, t, image, variance_noise=noise).prev_sample
             finally:
                 stream.close()
@@ -265,19 +282,27 @@ class DDPMPipeline(_PipelineBase):
 class DDIMPipeline(_PipelineBase):
     _class_name = "DDIMPipeline"
     _scheduler_cls = DDIMScheduler
+    _kept_scheduler_classes = (DPMSolverMultistepScheduler,)
 
     @torch.no_grad()
     def __call__(self, batch_size: int = 1, generator=None, eta: float = 0.0, num_inference_steps: int = 50,
                  use_clipped_model_output=None, output_type="pil", return_dict: bool = True, shard=None):
         if self.device.type != "cuda":
             raise RuntimeError("DDIMPipeline runs on the MI355X HIP engine only: call .to('cuda') first")
+        dpm = _is_dpmsolver(self.scheduler)
+        if dpm and shard is not None and self.scheduler.needs_step_noise and self.scheduler.noise_mode == "device":
+            raise NotImplementedError("DDIMPipeline: shard= with the SDE solver's device noise (every rank would generate "
+                                      "the same tensor for different rows)")
         image = self._initial_noise(batch_size, generator, shard)
         self.scheduler.set_timesteps(num_inference_steps)
         ts = [int(t) for t in self.scheduler.timesteps]
         tdev = _device_timestep_rows(self.scheduler.timesteps, image.shape[0], self.device)
         for i, t in enumerate(ts):
             eps = self.unet(image, tdev[i]).sample
-            image = self.scheduler.step(eps, t, image, eta=eta, generator=generator).prev_sample
+            if dpm:     # (no eta in its signature; its SDE variant draws each step's noise from `generator`, as eta > 0 does)
+                image = self.scheduler.step(eps, t, image, generator=generator).prev_sample
+            else:
+                image = self.scheduler.step(eps, t, image, eta=eta, generator=generator).prev_sample
         return self._finish(image, output_type, return_dict)
 
 

@@ -1,5 +1,6 @@
-"""``DDPMScheduler`` / ``DDIMScheduler`` with the diffusers-0.20.0 protocol DriveSceneGen uses, and ``RePaintScheduler``
-(scene completion with the same unconditional network; diffusers 0.20.0 ships it next to the other two).
+"""``DDPMScheduler`` / ``DDIMScheduler`` with the diffusers-0.20.0 protocol DriveSceneGen uses, ``RePaintScheduler``
+(scene completion with the same unconditional network) and ``DPMSolverMultistepScheduler`` (DPM-Solver++: the same network in
+a fraction of the steps); diffusers 0.20.0 ships both next to the other two.
 
 Reference call sites: /root/reference/DriveSceneGen/scripts/train.py:65 (``DDPMScheduler()``, all defaults),
 training_pipeline.py:76 (``.num_train_timesteps`` as a direct attribute), training_pipeline.py:80 and
@@ -10,7 +11,7 @@ Formulas: SURVEY.md App. A.3 / A.3b.
 Host side (this file): the beta / alpha-bar tables, the integer timestep tables and the per-step fp32
 scalars, computed with the same fp32 operation order as the reference so they are bit-identical.
 Device side: the elementwise tensor math, in libdsg.so (dsg_add_noise / dsg_ddpm_step / dsg_ddim_step / dsg_repaint_step /
-dsg_repaint_undo).
+dsg_repaint_undo / dsg_dpmsolver_step).
 """
 from __future__ import annotations
 
@@ -72,6 +73,8 @@ class DDPMScheduler:
                      trained_betas=None, variance_type="fixed_small", clip_sample=True, prediction_type="epsilon",
                      thresholding=False, dynamic_thresholding_ratio=0.995, clip_sample_range=1.0,
                      sample_max_value=1.0, timestep_spacing="leading", steps_offset=0)
+    # config keys this engine runs at their default value only
+    _fixed_keys = ("beta_schedule", "trained_betas", "prediction_type", "thresholding", "timestep_spacing")
 
     def __init__(self, **kwargs):
         cfg = dict(self._defaults)
@@ -79,7 +82,7 @@ class DDPMScheduler:
         if unknown:
             raise TypeError(f"{self._class_name}: unexpected arguments {sorted(unknown)}")
         cfg.update(kwargs)
-        for key in ("beta_schedule", "trained_betas", "prediction_type", "thresholding", "timestep_spacing"):
+        for key in self._fixed_keys:
             if key in cfg and cfg[key] != self._defaults[key]:
                 raise NotImplementedError(f"{self._class_name}: {key}={cfg[key]!r} is outside the DriveSceneGen "
                                           f"path (supported: {self._defaults[key]!r})")
@@ -252,9 +255,13 @@ class DDPMScheduler:
         return cls(**cfg)
 
     @classmethod
-    def from_config(cls, config):
+    def from_config(cls, config, **overrides):
+        """A scheduler of THIS class from another's config: keys this class lacks are dropped (diffusers' swap idiom,
+        ``pipe.scheduler = Other.from_config(pipe.scheduler.config)``); `overrides` replace or add entries, as in diffusers."""
         cfg = config.to_dict() if hasattr(config, "to_dict") else dict(config)
-        return cls(**{k: v for k, v in cfg.items() if k in cls._defaults})
+        cfg = {k: v for k, v in cfg.items() if k in cls._defaults}
+        cfg.update(overrides)
+        return cls(**cfg)
 
 
 class DDIMScheduler(DDPMScheduler):
@@ -316,6 +323,38 @@ class DDIMScheduler(DDPMScheduler):
         return SchedulerOutput(prev_sample=prev)
 
 
+class _NoiseSource:
+    """Where a scheduler's per-step noise comes from (``RePaintScheduler``, ``DPMSolverMultistepScheduler``): the caller's
+    generator (the default), or the Philox tensors (seed, offset), (seed, offset + 1), ... of ``dsg_philox_normal``, generated
+    inside the step kernel -- the same distribution, not the same values."""
+
+    noise_mode, noise_seed, noise_offset = "host", None, 0
+
+    def use_host_noise(self):
+        self.noise_mode, self.noise_seed, self.noise_offset = "host", None, 0
+
+    def use_device_noise(self, seed: int, offset: int = 0):
+        """Every later draw is the Philox4x32-10 / Box-Muller tensor (seed, offset), (seed, offset + 1), ... of
+        ``dsg_philox_normal`` (same distribution as the host mode, not the same values)."""
+        if seed is None:
+            raise ValueError(f"{self._class_name}: noise='device' needs an integer seed")
+        self.noise_mode, self.noise_seed, self.noise_offset = "device", int(seed) & (2 ** 64 - 1), int(offset)
+
+    def _next_offset(self):
+        k, self.noise_offset = self.noise_offset, self.noise_offset + 1
+        return k & (2 ** 64 - 1)
+
+    def device_randn(self, shape, device):
+        """One device-mode draw as a tensor of its own (the pipeline's x_T): ``dsg_philox_normal`` at the next offset."""
+        if self.noise_mode != "device":
+            raise RuntimeError(f"{self._class_name}.device_randn: call use_device_noise(seed) first")
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+        with torch.cuda.device(out.device):
+            _lib.check(_lib.load().dsg_philox_normal(_lib.ptr(out), out.numel(), self.noise_seed, self._next_offset(),
+                                                    _lib.stream_ptr(out.device)))
+        return out
+
+
 def _broadcast_extents(name, t, full, free):
     """`t` must be a 4-d tensor whose extents equal `full` except, on the axes listed in `free`, where 1 is allowed."""
     if t.dim() != 4 or any(int(t.shape[i]) != full[i] and not (i in free and int(t.shape[i]) == 1) for i in range(4)):
@@ -323,7 +362,7 @@ def _broadcast_extents(name, t, full, free):
         raise ValueError(f"RePaintScheduler.step: {name} has shape {tuple(t.shape)}, expected {allowed}")
 
 
-class RePaintScheduler(DDIMScheduler):
+class RePaintScheduler(DDIMScheduler, _NoiseSource):
     """diffusers-0.20.0 ``RePaintScheduler`` (Lugmayr et al., "RePaint: Inpainting using Denoising Diffusion Probabilistic
     Models", CVPR 2022, Algorithm 1): the DDIM-form reverse step of an UNCONDITIONAL network with the known region replaced,
     at every step, by the original noised to that step's level, and ``undo_step`` -- the jump back in time that lets the
@@ -355,31 +394,6 @@ class RePaintScheduler(DDIMScheduler):
         self.eta = float(self.config.eta)       # (diffusers: the pipeline overwrites this attribute per call)
         self._undo_cache = {}
         self.noise_mode, self.noise_seed, self.noise_offset = "host", None, 0
-
-    # ---- noise source -----------------------------------------------------------------------------------------
-    def use_host_noise(self):
-        self.noise_mode, self.noise_seed, self.noise_offset = "host", None, 0
-
-    def use_device_noise(self, seed: int, offset: int = 0):
-        """Every later draw is the Philox4x32-10 / Box-Muller tensor (seed, offset), (seed, offset + 1), ... of
-        ``dsg_philox_normal`` (see the class docstring: same distribution as the host mode, not the same values)."""
-        if seed is None:
-            raise ValueError("RePaintScheduler: noise='device' needs an integer seed")
-        self.noise_mode, self.noise_seed, self.noise_offset = "device", int(seed) & (2 ** 64 - 1), int(offset)
-
-    def _next_offset(self):
-        k, self.noise_offset = self.noise_offset, self.noise_offset + 1
-        return k & (2 ** 64 - 1)
-
-    def device_randn(self, shape, device):
-        """One device-mode draw as a tensor of its own (the pipeline's x_T): ``dsg_philox_normal`` at the next offset."""
-        if self.noise_mode != "device":
-            raise RuntimeError("RePaintScheduler.device_randn: call use_device_noise(seed) first")
-        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
-        with torch.cuda.device(out.device):
-            _lib.check(_lib.load().dsg_philox_normal(_lib.ptr(out), out.numel(), self.noise_seed, self._next_offset(),
-                                                    _lib.stream_ptr(out.device)))
-        return out
 
     # ---- timestep table ---------------------------------------------------------------------------------------
     def set_timesteps(self, num_inference_steps: int, jump_length: int = 10, jump_n_sample: int = 10, device=None):
@@ -516,3 +530,226 @@ class RePaintScheduler(DDIMScheduler):
                     host.consumed.record(torch.cuda.current_stream(x.device))
                 x = out
         return x
+
+
+class DPMSolverMultistepScheduler(DDPMScheduler, _NoiseSource):
+    """diffusers-0.20.0 ``DPMSolverMultistepScheduler`` (Lu et al., "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion
+    Probabilistic Models", 2022) in its data-prediction forms: ``algorithm_type`` "dpmsolver++" (the multistep exponential
+    integrator of the diffusion ODE, orders 1-3; order 1 is DDIM) and "sde-dpmsolver++" (orders 1-2, one noise tensor per
+    step).  One network call per step, like DDIM, at a higher order of accuracy in the step size: the sampler a diffusers
+    user swaps in to cut the step count, ``pipe.scheduler = DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)``.
+    diffusers is not installed where this project builds and the reference tree holds no DPM-Solver code: include/dsg.h
+    (``dsg_dpmsolver_step``), the paper and tests/dpmsolver_oracle.py are the specification.
+
+    Host side: the timestep table, the order bookkeeping and the per-step fp32 scalars (0-d fp32 torch arithmetic, memoised).
+    Device side: ONE ``dsg_dpmsolver_step`` per step -- it makes the data prediction, stores it as the newest history entry
+    and consumes it in the same pass.  The history is a ring of ``solver_order`` device buffers: the entry that falls out of
+    the history is the one the kernel writes, so no output aliases an input.
+
+    Noise (SDE variant only), as in ``RePaintScheduler``: by default drawn from the caller's generator in diffusers' order
+    and shape, or handed in as ``variance_noise`` (a device tensor or a ``HostNoise``); after ``use_device_noise(seed)`` draw k
+    is the Philox tensor (seed, offset + k), generated inside the step kernel.
+
+    Not built (raising): Karras sigmas, dynamic thresholding, the noise-prediction forms "dpmsolver" / "sde-dpmsolver",
+    v-prediction, learned variances.  ``variance_type`` "fixed_small" / "fixed_large" (what a converted DDPM config carries) are
+    accepted: as in diffusers, only the learned forms would change this scheduler's arithmetic."""
+
+    _class_name = "DPMSolverMultistepScheduler"
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
+                     sample_max_value=1.0, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
+                     use_karras_sigmas=False, lambda_min_clipped=-float("inf"), variance_type=None,
+                     timestep_spacing="linspace", steps_offset=0)
+    _fixed_keys = ("beta_schedule", "trained_betas", "prediction_type", "thresholding", "dynamic_thresholding_ratio",
+                   "sample_max_value", "use_karras_sigmas", "lambda_min_clipped")
+    _choices = dict(solver_order=(1, 2, 3), algorithm_type=("dpmsolver++", "sde-dpmsolver++"), solver_type=("midpoint", "heun"),
+                    lower_order_final=(True, False), timestep_spacing=("linspace", "leading", "trailing"),
+                    variance_type=(None, "fixed_small", "fixed_large"))
+
+    def _check_extra(self, cfg):
+        for key, allowed in self._choices.items():
+            v = cfg[key]
+            if isinstance(v, bool) != isinstance(allowed[0], bool) or v not in allowed:
+                raise NotImplementedError(f"{self._class_name}: {key}={v!r} is outside the DriveSceneGen path "
+                                          f"(supported: {allowed!r})")
+        if isinstance(cfg["steps_offset"], bool) or not isinstance(cfg["steps_offset"], (int, np.integer)):
+            raise NotImplementedError(f"{self._class_name}: steps_offset={cfg['steps_offset']!r} is outside the DriveSceneGen "
+                                      "path (supported: an integer)")
+        if cfg["algorithm_type"] == "sde-dpmsolver++" and cfg["solver_order"] == 3:
+            raise NotImplementedError(f"{self._class_name}: algorithm_type='sde-dpmsolver++' has orders 1 and 2 only "
+                                      "(solver_order=3 is outside the DriveSceneGen path)")
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self.timesteps = torch.from_numpy(np.linspace(0, self.config.num_train_timesteps - 1, self.config.num_train_timesteps,
+                                                      dtype=np.float32)[::-1].copy().astype(np.int64))
+        self.lower_order_nums = 0
+        self._hist_t = []                       # timesteps of the history entries, newest first
+        self._ring, self._head = None, 0        # solver_order device buffers; _ring[_head] holds the newest entry
+        self._index = None
+        self.use_host_noise()
+
+    @property
+    def needs_step_noise(self):
+        """Does ``step`` consume one noise tensor per call?  (what a pipeline's noise stream has to count)"""
+        return self.config.algorithm_type == "sde-dpmsolver++"
+
+    # ---- timestep table ---------------------------------------------------------------------------------------
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        n_train, n = self.config.num_train_timesteps, int(num_inference_steps)
+        if n < 1 or n > n_train:
+            raise ValueError(f"num_inference_steps {num_inference_steps} outside [1, num_train_timesteps {n_train}]")
+        spacing = self.config.timestep_spacing
+        if spacing == "linspace":
+            ts = np.linspace(0, n_train - 1, n + 1).round()[::-1][:-1]
+        elif spacing == "leading":
+            ts = (np.arange(0, n + 1) * (n_train // (n + 1))).round()[::-1][:-1] + self.config.steps_offset
+        else:
+            ts = np.arange(n_train, 0, -n_train / n).round() - 1
+        ts = ts.copy().astype(np.int64)
+        _, first = np.unique(ts, return_index=True)          # drop duplicates, keep the order
+        ts = ts[np.sort(first)]
+        if ts.min() < 0 or ts.max() >= n_train:
+            raise ValueError(f"{self._class_name}: steps_offset={self.config.steps_offset} puts a timestep outside "
+                             f"[0, {n_train - 1}]")
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self.num_inference_steps = len(ts)
+        self._index = {int(t): i for i, t in enumerate(ts)}
+        self._hist_t, self.lower_order_nums = [], 0
+
+    # ---- order bookkeeping and scalars ----------------------------------------------------------------------------
+    def _order_at(self, i: int) -> int:
+        """The order the step at index `i` of the table uses, given ``lower_order_nums`` history entries so far."""
+        so, L = self.config.solver_order, len(self.timesteps)
+        short = self.config.lower_order_final and L < 15
+        if so == 1 or self.lower_order_nums < 1 or (i == L - 1 and short):
+            return 1
+        if so == 2 or self.lower_order_nums < 2 or (i == L - 2 and short):
+            return 2
+        return 3
+
+    def step_scalars(self, s0: int, t: int, s1=None, s2=None, order: int = 1):
+        """The fp32 scalars ``dsg_dpmsolver_step`` takes for the step s0 -> t that uses `order`, with the history entries made
+        at s1 and s2 (memoised: some twenty 0-d tensor operations otherwise)."""
+        key = (s0, t, s1 if order >= 2 else None, s2 if order >= 3 else None, order, self.config.algorithm_type,
+               self.config.solver_type)
+        hit = self._scalar_cache.get(key)
+        if hit is None:
+            hit = self._scalar_cache[key] = self._step_scalars(s0, t, s1, s2, order)
+        return hit
+
+    def _step_scalars(self, s0, t, s1, s2, order):
+        lam, al, sg = self.lambda_t, self.alpha_t, self.sigma_t
+        sde = self.config.algorithm_type == "sde-dpmsolver++"
+        heun = self.config.solver_type == "heun"
+        alpha_t, sigma_t, sigma_s0 = al[t], sg[t], sg[s0]
+        h = lam[t] - lam[s0]
+        out = dict(sigma_s=sigma_s0, alpha_s=al[s0], inv_r0=0.0, inv_r1=0.0, q=0.0, p=0.0, c1=0.0, c2=0.0, cn=0.0)
+        if order >= 2:
+            h0 = lam[s0] - lam[s1]
+            r0 = h0 / h
+            out["inv_r0"] = 1.0 / r0
+        if order == 3:
+            h1 = lam[s1] - lam[s2]
+            r1 = h1 / h
+            out["inv_r1"] = 1.0 / r1
+            out["q"] = r0 / (r0 + r1)
+            out["p"] = 1.0 / (r0 + r1)
+        if not sde:
+            E = torch.exp(-h) - 1.0
+            out["kx"] = sigma_t / sigma_s0
+            out["c0"] = -(alpha_t * E)
+            if order == 2 and not heun:
+                out["c1"] = -(0.5 * (alpha_t * E))
+            elif order >= 2:
+                out["c1"] = alpha_t * (E / h + 1.0)
+            if order == 3:
+                out["c2"] = -(alpha_t * ((E + h) / h ** 2 - 0.5))
+        else:
+            G = 1.0 - torch.exp(-2.0 * h)
+            out["kx"] = sigma_t / sigma_s0 * torch.exp(-h)
+            out["c0"] = alpha_t * G
+            if order == 2:
+                out["c1"] = alpha_t * (G / (-2.0 * h) + 1.0) if heun else 0.5 * (alpha_t * G)
+            out["cn"] = sigma_t * torch.sqrt(G)
+        return {k: float(v) for k, v in out.items()}
+
+    # ---- the step ---------------------------------------------------------------------------------------------
+    def _history(self, like):
+        """The ring of ``solver_order`` history buffers for samples like `like` (allocated on first use, and again when the
+        shape or the device changes -- which is only legal at the start of a run)."""
+        r = self._ring
+        if r is None or r[0].shape != like.shape or r[0].device != like.device:
+            if self.lower_order_nums > 0:
+                raise ValueError(f"{self._class_name}.step: the sample changed shape or device in the middle of a run "
+                                 "(call set_timesteps to start another)")
+            self._ring = [torch.empty_like(like) for _ in range(self.config.solver_order)]
+            self._head = 0
+        return self._ring
+
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict: bool = True):
+        if not sample.is_cuda:
+            raise RuntimeError(f"{self._class_name}.step runs on the MI355X HIP engine only (got a CPU tensor)")
+        if sample.dtype != torch.float32 or model_output.dtype != torch.float32:
+            raise ValueError(f"{self._class_name}.step: fp32 only")
+        if tuple(model_output.shape) != tuple(sample.shape):
+            raise ValueError(f"{self._class_name}.step: model output {tuple(model_output.shape)} != sample {tuple(sample.shape)}")
+        if self._index is None:
+            raise ValueError(f"{self._class_name}.step: call set_timesteps first")
+        ts = self.timesteps
+        L = len(ts)
+        s0 = int(timestep)
+        i = self._index.get(s0, L - 1)          # (diffusers: a timestep the table lacks is taken for the last one)
+        t = int(ts[i + 1]) if i + 1 < L else 0
+        order = self._order_at(i)
+        s1 = self._hist_t[0] if order >= 2 else None
+        s2 = self._hist_t[1] if order >= 3 else None
+        s = self.step_scalars(s0, t, s1, s2, order)
+        x, e = sample.contiguous(), model_output.contiguous()
+        full = tuple(x.shape)
+        ring = self._history(x)
+        K = len(ring)
+        m1 = ring[self._head] if order >= 2 else None
+        m2 = ring[(self._head - 1) % K] if order >= 3 else None
+        slot = (self._head + 1) % K if self._hist_t else self._head     # the entry that falls out of the history
+        noise, host, nptr, seed, offset = None, None, None, 0, 0
+        sde = self.needs_step_noise
+        if sde:
+            if isinstance(variance_noise, HostNoise):
+                host = variance_noise
+                if tuple(host.shape) != full:
+                    raise ValueError(f"variance_noise has shape {tuple(host.shape)}, the sample {full}")
+                nptr = host.device_ptr
+            elif variance_noise is not None:
+                noise = variance_noise.to(x.device, torch.float32).contiguous()
+                if tuple(noise.shape) != full:
+                    raise ValueError(f"variance_noise has shape {tuple(noise.shape)}, the sample {full}")
+                nptr = _lib.ptr(noise)
+            elif self.noise_mode == "device":
+                seed, offset = self.noise_seed, self._next_offset()
+            else:
+                noise = _randn_like_reference(model_output.shape, generator, model_output.device,
+                                              model_output.dtype).contiguous()
+                nptr = _lib.ptr(noise)
+        prev = torch.empty_like(x)
+        a = _lib.DpmSolverStepArgs(
+            sample=_lib.ptr(x), eps=_lib.ptr(e), m1=_lib.ptr(m1), m2=_lib.ptr(m2), noise=nptr, prev=_lib.ptr(prev),
+            m0_out=_lib.ptr(ring[slot]), noise_out=None, numel=x.numel(), order=order, add_noise=int(sde),
+            sigma_s=s["sigma_s"], alpha_s=s["alpha_s"], inv_r0=s["inv_r0"], inv_r1=s["inv_r1"], q=s["q"], p=s["p"],
+            kx=s["kx"], c0=s["c0"], c1=s["c1"], c2=s["c2"], cn=s["cn"], seed=seed, offset=offset)
+        import ctypes
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().dsg_dpmsolver_step(ctypes.byref(a), _lib.stream_ptr(x.device)))
+            if host is not None:
+                host.consumed = torch.cuda.Event()
+                host.consumed.record(torch.cuda.current_stream(x.device))
+        self._head = slot
+        self._hist_t = ([s0] + self._hist_t)[:K]
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
+        if not return_dict:
+            return (prev,)
+        return SchedulerOutput(prev_sample=prev)

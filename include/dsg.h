@@ -407,6 +407,40 @@ typedef struct {
 int dsg_repaint_step(const dsg_repaint_step_args* args, void* stream);
 int dsg_repaint_undo(const float* sample, const float* noise /* NULL: Philox (seed, offset) */, float* out, int64_t numel,
                      float ck, float cz, uint64_t seed, uint64_t offset, void* stream);
+/* DPM-Solver++ multistep (Lu et al., "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models", 2022;
+ * diffusers 0.20.0 DPMSolverMultistepScheduler.step, algorithm types "dpmsolver++" and "sde-dpmsolver++", orders 1-3): the
+ * tensor side of one solver step as ONE pass over `numel` floats -- the data prediction is made, stored as the history entry
+ * this step adds and consumed in the same pass.  Per element, every operation rounded to fp32 on its own, in exactly this order
+ * (the contract tests/test_gpu_dpmsolver.py pins):
+ *     m0   = (x - sigma_s*e) / alpha_s                          -> m0_out
+ *     D10  = inv_r0*(m0 - m1)                                   order >= 2
+ *     D11  = inv_r1*(m1 - m2);  dd = D10 - D11;
+ *     D1   = D10 + q*dd;  D2 = p*dd                             order 3   (D1 = D10 at order 2)
+ *     prev = kx*x + c0*m0  [+ c1*D1]  [+ c2*D2]  [+ cn*z]       summed left to right; the z term when add_noise != 0
+ * The scalars are the host's (signed: the kernel only adds).  m1 / m2 are the data predictions of the previous two steps; they
+ * may be NULL where the order does not read them.  z is one standard normal per element with dsg_repaint_step's sources: `noise`
+ * != NULL -- device memory or device-accessible pinned host memory, read once; `noise` == NULL with add_noise != 0 -- generated
+ * in the kernel, element e = element e of dsg_philox_normal(numel, seed, offset), bit for bit.  `noise_out` (optional) receives
+ * the z that was used.  With add_noise == 0, `noise` and `noise_out` are not touched.  All pointers 16-byte aligned: every
+ * stream moves as dwordx4 (the last numel % 4 elements singly); otherwise dword accesses.  `prev`, `m0_out` and `noise_out` must
+ * not overlap any input or each other.  Arguments are checked before any HIP call (NULL pointers, order, a missing history
+ * entry, overlap, numel <= 0).  Stream-asynchronous, no allocation, legal under stream capture. */
+typedef struct {
+  const float* sample;      /* x at the current timestep [numel] */
+  const float* eps;         /* model output              [numel] */
+  const float* m1;          /* data prediction of the previous step (order >= 2) */
+  const float* m2;          /* ... of the step before that          (order 3)    */
+  const float* noise;       /* [numel], or NULL: Philox (seed, offset); read only when add_noise != 0 */
+  float* prev;              /* x at the next timestep    [numel] */
+  float* m0_out;            /* this step's data prediction [numel] */
+  float* noise_out;         /* optional [numel] */
+  int64_t numel;
+  int32_t order;            /* 1, 2 or 3: the order USED at this step */
+  int32_t add_noise;
+  float sigma_s, alpha_s, inv_r0, inv_r1, q, p, kx, c0, c1, c2, cn;
+  uint64_t seed, offset;
+} dsg_dpmsolver_step_args;
+int dsg_dpmsolver_step(const dsg_dpmsolver_step_args* args, void* stream);
 /* Pipeline post-process (DDPMPipeline.__call__ tail, App. A.4): (x/2+0.5).clamp(0,1), NCHW -> NHWC;
  * mode 0: float out; mode 1: uint8 round (generation.py `.images`); mode 2: uint8 truncation
  * (training_pipeline.py:21-22). */
