@@ -9,6 +9,7 @@ from .schedulers import DDPMScheduler, DDIMScheduler, DPMSolverMultistepSchedule
 from .pipelines import DDPMPipeline, DDIMPipeline, RePaintPipeline, ImagePipelineOutput  # noqa: F401
 from .optimization import get_cosine_schedule_with_warmup  # noqa: F401
 from .train_loop import fit, notebook_launcher, sample_to_pil  # noqa: F401
+from .ema import EMAModel  # noqa: F401
 from .training import AdamW, Accelerator, GradBuckets, clip_grad_norm_, mse_loss  # noqa: F401
 
 __version__ = "0.1.0"

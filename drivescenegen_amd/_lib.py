@@ -104,6 +104,11 @@ class DpmSolverStepArgs(C.Structure):
     ]
 
 
+class EmaJob(C.Structure):
+    """Mirror of ``dsg_ema_job`` (include/dsg.h)."""
+    _fields_ = [("param", C.c_void_p), ("shadow", C.c_void_p), ("numel", C.c_int64), ("copy_only", C.c_int32), ("pad", C.c_int32)]
+
+
 class UNetConfig(C.Structure):
     """Mirror of ``dsg_unet_config`` (include/dsg.h)."""
     _fields_ = [
@@ -224,6 +229,8 @@ SIGNATURES = {
     "dsg_l2_norm": [_vp, _i64, _vp, _vp, _sz, _vp],
     "dsg_clip_scale": [_vp, _i64, _vp, _f32, _vp],
     "dsg_adamw_step": [_vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _vp, _f32, _vp],
+    "dsg_ema_job_chunks": [C.POINTER(EmaJob), C.POINTER(_i64)],
+    "dsg_ema_step": [_vp, _vp, _i32, _i64, _f32, _vp],
     "dsg_resize_normalize_u8": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _vp],
     "dsg_resize_normalize_f32": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _vp],
     "dsg_png_probe": [C.c_char_p, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],

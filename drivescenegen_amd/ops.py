@@ -867,6 +867,68 @@ def adamw_step_(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), 
                                              _lib.ptr(total_norm), float(max_norm), _st(param)))
 
 
+class EmaTable:
+    """A device-resident job table for dsg_ema_step.  jobs: [(param_ptr, shadow_ptr, numel, copy_only)], device addresses of
+    fp32 elements; the memory must stay where it is while the table is in use.  Neighbouring jobs that are contiguous in BOTH
+    buffers and agree on copy_only are merged (``merge=False`` keeps one job per entry): the arithmetic is per element, so
+    the bits do not depend on where the job boundaries are, and this is why the library has one table-driven kernel and no
+    second flat one -- parameters that sit in one slab at the shadow's own offsets are a table of one job."""
+
+    def __init__(self, jobs, device, merge: bool = True):
+        rows = []
+        for pp, sp, n, co in jobs:
+            pp, sp, n, co = int(pp), int(sp), int(n), int(bool(co))
+            if merge and rows and rows[-1][3] == co and rows[-1][0] + 4 * rows[-1][2] == pp and rows[-1][1] + 4 * rows[-1][2] == sp:
+                rows[-1][2] += n
+            else:
+                rows.append([pp, sp, n, co])
+        lib = _lib.load()
+        self.n = len(rows)
+        self.rows = tuple(tuple(r) for r in rows)
+        self.device = torch.device(device)
+        arr = (_lib.EmaJob * max(self.n, 1))()
+        first = [0]
+        for j, (pp, sp, n, co) in zip(arr, rows):
+            j.param, j.shadow, j.numel, j.copy_only = pp, sp, n, co
+            chunks = C.c_int64()
+            _lib.check(lib.dsg_ema_job_chunks(C.byref(j), C.byref(chunks)))
+            first.append(first[-1] + chunks.value)
+        self.total = first[-1]
+        self.jobs = self.first = None
+        if self.n:
+            if self.device.type != "cuda":
+                raise RuntimeError("drivescenegen_amd: the HIP engine needs GPU tensors (got a CPU tensor); there is no CPU fallback")
+            self.jobs = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+            self.first = torch.tensor(first, dtype=torch.int64).to(self.device)
+
+    def run(self, one_minus_decay):
+        """shadow <- shadow - one_minus_decay * (shadow - param) on every job (copy_only jobs: shadow <- param), ONE launch."""
+        if not self.n:
+            return
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().dsg_ema_step(self.jobs.data_ptr(), self.first.data_ptr(), self.n, self.total,
+                                                float(one_minus_decay), _lib.stream_ptr(self.device)))
+
+
+def ema_step_(params, shadows, one_minus_decay, copy_only=None, merge: bool = True):
+    """diffusers 0.20.0 ``EMAModel.step`` arithmetic on lists of contiguous fp32 GPU tensors, in place on `shadows`, one launch.
+    copy_only[i] true: shadows[i] <- params[i] (a parameter with requires_grad False).  Builds a table per call;
+    ``EMAModel`` keeps its table."""
+    params, shadows = list(params), list(shadows)
+    copy_only = [False] * len(params) if copy_only is None else list(copy_only)
+    if not (len(params) == len(shadows) == len(copy_only)):
+        raise ValueError("ema_step_: params, shadows and copy_only differ in length")
+    jobs = []
+    for p, s, co in zip(params, shadows, copy_only):
+        if p.dtype != torch.float32 or s.dtype != torch.float32 or p.numel() != s.numel():
+            raise ValueError("ema_step_: every (param, shadow) pair must be fp32 with equal element counts")
+        if p.numel():
+            jobs.append((_lib.ptr(p), _lib.ptr(s), p.numel(), co))
+    table = EmaTable(jobs, shadows[0].device if shadows else "cpu", merge=merge)
+    table.run(one_minus_decay)
+    return table
+
+
 def scale(x, alpha_dev=None, mult=1.0, out=None):
     """out = x * alpha_dev[0] * mult (in place when out is x)."""
     out = torch.empty_like(x) if out is None else out

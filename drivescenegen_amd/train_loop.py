@@ -141,10 +141,12 @@ class DeviceNoise:
         return off
 
 
-def train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=None):
+def train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=None, ema=None):
     """One optimisation step on a clean batch [B, C, H, W] in [-1, 1]; returns the detached loss (a device scalar).
     `noise`: the step's N(0,1) tensor on the batch's device when the caller drew it ahead (``NoiseAhead``); a
-    ``DeviceNoise`` for the opt-in library generator; drawn here, on the host, otherwise -- the reference's own order."""
+    ``DeviceNoise`` for the opt-in library generator; drawn here, on the host, otherwise -- the reference's own order.
+    `ema`: an ``EMAModel`` averaged after every optimizer step (one launch), where diffusers' train_unconditional.py calls
+    ``ema_model.step(model.parameters())`` -- on synchronising steps only, a step the fp16 GradScaler skipped included."""
     t = None
     if isinstance(noise, DeviceNoise):
         t = torch.randint(0, noise_scheduler.num_train_timesteps, (batch.shape[0],), device=batch.device).long()
@@ -161,6 +163,8 @@ def train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, bat
         optimizer.step()
         lr_scheduler.step()
         optimizer.zero_grad()
+        if ema is not None and accelerator.sync_gradients:
+            ema.step(model.parameters())
     return loss.detach()
 
 
@@ -184,29 +188,33 @@ def batches_with_noise(batches, overlap_noise: bool = True):
 
 
 def train_steps(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batches, overlap_noise: bool = True,
-                noise="host"):
+                noise="host", ema=None):
     """Generator over one pass of `batches` (an epoch's loader): yields each step's detached loss.  Batch k+1 is fetched and
     its noise draw handed to the worker thread before step k's kernels are queued, so the host draw overlaps the GPU.
-    ``noise="device"`` (or a ``DeviceNoise``): the library's counter-based generator instead of the host draw (opt-in)."""
+    ``noise="device"`` (or a ``DeviceNoise``): the library's counter-based generator instead of the host draw (opt-in).
+    `ema`: see ``train_step``."""
     if noise != "host":
         gen = noise if isinstance(noise, DeviceNoise) else DeviceNoise(rank=getattr(accelerator, "process_index", 0))
         if noise != "device" and not isinstance(noise, DeviceNoise):
             raise ValueError(f"train_steps: noise must be 'host', 'device' or a DeviceNoise (got {noise!r})")
         for batch in batches:
-            yield train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=gen)
+            yield train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=gen, ema=ema)
         return
     for batch, nz in batches_with_noise(batches, overlap_noise):
-        yield train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=nz)
+        yield train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=nz, ema=ema)
 
 
 def fit(config, model, noise_scheduler, optimizer, train_dataloader, lr_scheduler, sample_steps: int = 750,
-        on_step=None, overlap_noise: bool = True, noise="host"):
+        on_step=None, overlap_noise: bool = True, noise="host", ema=None):
     """Train for ``config.num_epochs`` epochs.  `config` carries the reference's TrainingConfig fields (train.py:13-29):
     mixed_precision, gradient_accumulation_steps, output_dir, num_epochs, save_image_epochs, save_model_epochs,
     eval_batch_size, seed.  Returns the number of optimisation steps taken on this rank.  `overlap_noise=False` draws each
     step's noise on the critical path like the reference does (same values either way).  ``noise="device"``: the library's
     counter-based generator (seeded from ``config.seed``; one stream per rank and step) instead of the host draw -- opt-in,
-    not the reference's values."""
+    not the reference's values.  `ema`: an ``EMAModel`` of the model's parameters (opt-in, as in diffusers'
+    train_unconditional.py): averaged after every optimizer step; the per-epoch sample and the saved pipeline then use the
+    AVERAGED weights (store, copy_to, sample and save, restore), ``<output_dir>/unet_ema`` is written with
+    ``ema.save_pretrained`` at every model save, and training goes on from the raw weights, bit for bit as without it."""
     accelerator = Accelerator(mixed_precision=config.mixed_precision,
                               gradient_accumulation_steps=config.gradient_accumulation_steps, log_with="tensorboard",
                               project_dir=os.path.join(config.output_dir, "logs"))
@@ -215,11 +223,14 @@ def fit(config, model, noise_scheduler, optimizer, train_dataloader, lr_schedule
         accelerator.init_trackers("train_example")
     model, optimizer, train_dataloader, lr_scheduler = accelerator.prepare(model, optimizer, train_dataloader, lr_scheduler)
     step = 0
+    if ema is not None and ema.model_cls is None:   # what ema.save_pretrained builds the averaged model from
+        unet = accelerator.unwrap_model(model)
+        ema.model_cls, ema.model_config = type(unet), unet.config
     if noise == "device":
         noise = DeviceNoise(seed=getattr(config, "seed", 0), rank=accelerator.process_index)
     for epoch in range(config.num_epochs):
         for loss in train_steps(accelerator, model, noise_scheduler, optimizer, lr_scheduler, train_dataloader, overlap_noise,
-                                noise=noise):
+                                noise=noise, ema=ema):
             record = {"loss": loss.item(), "lr": lr_scheduler.get_last_lr()[0], "step": step}
             accelerator.log(record, step=step)
             if on_step is not None:
@@ -227,11 +238,24 @@ def fit(config, model, noise_scheduler, optimizer, train_dataloader, lr_schedule
             step += 1
         last = epoch == config.num_epochs - 1
         if accelerator.is_main_process:
-            pipeline = DDPMPipeline(unet=accelerator.unwrap_model(model), scheduler=noise_scheduler)
-            if last or (epoch + 1) % config.save_image_epochs == 0:
-                write_sample(config, pipeline, sample_steps)
-            if last or (epoch + 1) % config.save_model_epochs == 0:
-                pipeline.save_pretrained(config.output_dir)
+            unet = accelerator.unwrap_model(model)
+            pipeline = DDPMPipeline(unet=unet, scheduler=noise_scheduler)
+            want_image = last or (epoch + 1) % config.save_image_epochs == 0
+            want_model = last or (epoch + 1) % config.save_model_epochs == 0
+            averaged = ema is not None and (want_image or want_model)
+            if averaged:
+                ema.store(unet.parameters())
+                ema.copy_to(unet.parameters())
+            try:
+                if want_image:
+                    write_sample(config, pipeline, sample_steps)
+                if want_model:
+                    pipeline.save_pretrained(config.output_dir)
+                    if ema is not None:
+                        ema.save_pretrained(os.path.join(config.output_dir, "unet_ema"))
+            finally:
+                if averaged:
+                    ema.restore(unet.parameters())
     accelerator.end_training()
     return step
 

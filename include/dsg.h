@@ -664,6 +664,32 @@ int dsg_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    const float* total_norm, float max_norm, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exponential moving average of the weights: diffusers 0.20.0 training_utils.EMAModel.step, which diffusers' own
+ * train_unconditional.py (the script the reference's loop, training_pipeline.py:46-107, is a trimmed copy of) calls after
+ * every optimizer step.  ONE launch updates every shadow parameter from every live parameter.  Per element
+ *     copy_only == 0 (requires_grad):   t = s - p;  u = one_minus_decay * t;  s = s - u      (each rounded to fp32 on its own:
+ *                                       `s_param.sub_(one_minus_decay * (s_param - param))`, the Python scalar taken as fp32)
+ *     copy_only != 0:                   s = p                                                (`s_param.copy_(param)`)
+ * Same bits as torch on the CPU.  A job is one (param, shadow) pair of `numel` fp32 elements; it is served in chunks of
+ * DSG_EMA_CHUNK elements, one workgroup each: chunks = ceil(numel / DSG_EMA_CHUNK) (dsg_ema_job_chunks, host-only).  The
+ * caller keeps two device arrays: the jobs and first[njobs + 1], the running sum of the jobs' chunk counts;
+ * total_chunks = first[njobs].  A job whose two pointers are both 16-byte aligned moves 16 bytes per lane, any other job
+ * 4 bytes per lane; no element outside [0, numel) of either buffer is read or written.  param and shadow of one job must
+ * not overlap, nor the shadows of two jobs.  njobs == 0 launches nothing.
+ * ---------------------------------------------------------------------------------------- */
+#define DSG_EMA_CHUNK 4096
+typedef struct {
+  const float* param;
+  float* shadow;
+  int64_t numel;
+  int32_t copy_only;
+  int32_t pad;
+} dsg_ema_job;
+int dsg_ema_job_chunks(const dsg_ema_job* job, int64_t* chunks);
+int dsg_ema_step(const dsg_ema_job* jobs_dev, const int64_t* first_dev, int32_t njobs, int64_t total_chunks,
+                 float one_minus_decay, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Host-side batch PNG decoder of the training feeder (row f1; NO device work, no stream): `threads` native threads decode
  * paths[0..n) into the rows of out[n][h][w][c] (uint8; the loader's PINNED staging buffer), status[i] = 0 or a per-file code
  * (1 cannot open, 2 not a PNG, 3 unsupported variant, 4 shape differs from (h, w, c), 5 damaged) -- the caller reads THOSE
