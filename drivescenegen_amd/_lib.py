@@ -197,6 +197,10 @@ SIGNATURES = {
     "dsg_add_noise_philox": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, C.c_uint64, C.c_uint64, _vp],
     "dsg_ddpm_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
     "dsg_ddim_step": [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp],
+    "dsg_dynthresh_workspace_bytes": [_i32, C.POINTER(_sz)],
+    "dsg_dynthresh_scale": [_vp, _vp, _vp, _i32, _i64, _f32, _f32, _i64, _i64, _f32, _f32, _vp, _sz, _vp],
+    "dsg_ddpm_step_thr": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _f32, _vp],
+    "dsg_ddim_step_thr": [_vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _vp],
     "dsg_repaint_step": [C.POINTER(RepaintStepArgs), _vp],
     "dsg_repaint_undo": [_vp, _vp, _vp, _i64, _f32, _f32, C.c_uint64, C.c_uint64, _vp],
     "dsg_dpmsolver_step": [C.POINTER(DpmSolverStepArgs), _vp],

@@ -356,6 +356,238 @@ __global__ __launch_bounds__(256) void dpmsolver_step_kernel(const float* __rest
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Dynamic thresholding (Saharia et al., "Imagen", 2022, section 2.3; diffusers 0.20.0 `_threshold_sample`): per sample, the
+// q-quantile of |p0| -- torch.quantile's linear interpolation between two neighbouring order statistics -- clamped into
+// [1, sample_max_value] is the scale s[n]; the step then uses clamp(p0, -s, s) / s in place of the statically clipped p0
+// (include/dsg.h states the arithmetic as the contract).  p0 is never stored: every pass recomputes it with pred_x0, the
+// function the step kernels use, so the bits agree.
+//
+// The two order statistics come from an exact MSB-first radix select on key = bits(|p0|) (sign bit clear: the pattern orders
+// like the value for everything that is no NaN; NaN patterns sort last and are counted apart), 11 + 11 + 9 bits:
+//   thr_hist_kernel<P>   every element whose key starts with the prefix chosen so far counts its next digit into a per-block LDS
+//                        histogram, which is flushed (non-zero bins) with integer atomics into the sample's global histogram;
+//   thr_scan_kernel<P>   one block per sample: finds the digit that holds each of the two ranks, extends the two prefixes,
+//                        rebases the two ranks, zeroes the histograms for the next pass; after the last pass the prefixes ARE
+//                        v_lo and v_hi, and it writes s[n].
+// The two ranks are neighbours (k_hi - k_lo <= 1) but may fall into different bins: from then on there are two prefixes and two
+// histograms.  While the prefixes agree only histogram 0 is kept.  Integer counts: the result does not depend on arrival order.
+// No loop here depends on the data, so NaN / Inf keys cannot keep a kernel from ending.
+// Workspace per sample (32-bit words): THR_STATE state words, then two histograms of THR_BINS.
+constexpr int THR_BINS = 2048;
+constexpr int THR_STATE = 16;      // [0] prefix_lo [1] prefix_hi [2] rank_lo [3] rank_hi [4] NaN seen
+constexpr int THR_WORDS = THR_STATE + 2 * THR_BINS;
+
+template <int PASS> struct thr_digit;
+template <> struct thr_digit<1> { static constexpr int shift = 20, bins = 2048, prefix_shift = 31; };
+template <> struct thr_digit<2> { static constexpr int shift = 9, bins = 2048, prefix_shift = 20; };
+template <> struct thr_digit<3> { static constexpr int shift = 0, bins = 512, prefix_shift = 9; };
+
+// One count per lane with `valid` into h[bin].  Called by all 64 lanes of a wave together.  When every valid lane names the same
+// bin (an all-equal row; real rasters, whose values sit in a few exponent bins, often) ONE lane adds the lane count: the LDS
+// atomic unit would otherwise serve the 64 adds to one address one after another.
+__device__ __forceinline__ void thr_count(uint32_t* h, uint32_t bin, bool valid) {
+  const unsigned long long m = __ballot(valid);
+  if (m == 0) return;
+  const int lead = __ffsll(m) - 1;
+  const uint32_t first = (uint32_t)__shfl((int)bin, lead);
+  if (__ballot(valid && bin != first) == 0) {
+    if ((int)(threadIdx.x & 63) == lead) atomicAdd(&h[first], (uint32_t)__popcll(m));
+  } else if (valid) {
+    atomicAdd(&h[bin], 1u);
+  }
+}
+
+template <int PASS>
+__device__ __forceinline__ void thr_count_key(uint32_t* h, uint32_t key, bool valid, uint32_t pfx_lo, uint32_t pfx_hi, bool two) {
+  typedef thr_digit<PASS> D;
+  const uint32_t bin = (key >> D::shift) & (uint32_t)(D::bins - 1);
+  if (PASS == 1) {
+    thr_count(h, bin, valid);
+  } else {
+    const uint32_t head = key >> D::prefix_shift;
+    thr_count(h, bin, valid && head == pfx_lo);
+    if (two) thr_count(h + THR_BINS, bin, valid && head == pfx_hi);      // (`two` is the same in every lane of the grid row)
+  }
+}
+
+// grid = (blocks per sample, n); a block walks its share of the sample's `per` elements 1024 at a time, 4 consecutive per lane
+template <int PASS, bool VEC>
+__global__ __launch_bounds__(256) void thr_hist_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                       uint32_t* __restrict__ ws, int64_t per, float sb, float sa) {
+  typedef thr_digit<PASS> D;
+  __shared__ uint32_t h[2 * THR_BINS];
+  __shared__ uint32_t nan_seen;
+  uint32_t* st = ws + (int64_t)blockIdx.y * THR_WORDS;
+  const uint32_t pfx_lo = PASS == 1 ? 0u : st[0], pfx_hi = PASS == 1 ? 0u : st[1];
+  const bool two = PASS != 1 && pfx_lo != pfx_hi;
+  for (int b = threadIdx.x; b < (two ? 2 : 1) * THR_BINS; b += 256) h[b] = 0;
+  if (threadIdx.x == 0) nan_seen = 0;
+  __syncthreads();
+  const float* xr = x + (int64_t)blockIdx.y * per;
+  const float* er = eps + (int64_t)blockIdx.y * per;
+  bool nan = false;
+  const int64_t stride = (int64_t)gridDim.x * 1024;
+  for (int64_t base = (int64_t)blockIdx.x * 1024; base < per; base += stride) {     // (the same trip count in every lane)
+    const int64_t i0 = base + (int64_t)threadIdx.x * 4;
+    float xv[4], ev[4];
+    if (VEC && i0 + 4 <= per) {
+      const float4 a = *reinterpret_cast<const float4*>(xr + i0);
+      const float4 c = *reinterpret_cast<const float4*>(er + i0);
+      xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+      ev[0] = c.x; ev[1] = c.y; ev[2] = c.z; ev[3] = c.w;
+    } else {
+      for (int j = 0; j < 4; ++j) {
+        const bool in = i0 + j < per;
+        xv[j] = in ? xr[i0 + j] : 0.f;
+        ev[j] = in ? er[i0 + j] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t key = __float_as_uint(pred_x0(xv[j], ev[j], sb, sa, 0.f)) & 0x7fffffffu;
+      const bool valid = i0 + j < per;
+      if (PASS == 1) nan = nan || (valid && key > 0x7f800000u);
+      thr_count_key<PASS>(h, key, valid, pfx_lo, pfx_hi, two);
+    }
+  }
+  if (PASS == 1 && nan) nan_seen = 1;        // (a benign race: every writer stores 1)
+  __syncthreads();
+  uint32_t* g = st + THR_STATE;
+  for (int b = threadIdx.x; b < D::bins; b += 256) {
+    const uint32_t c = h[b];
+    if (c) atomicAdd(&g[b], c);
+    if (two) {
+      const uint32_t c1 = h[THR_BINS + b];
+      if (c1) atomicAdd(&g[THR_BINS + b], c1);
+    }
+  }
+  if (PASS == 1 && threadIdx.x == 0 && nan_seen) atomicOr(&st[4], 1u);
+}
+
+// grid = n, 256 threads; thread t owns bins [t*PER, (t+1)*PER) of both histograms
+template <int PASS>
+__global__ __launch_bounds__(256) void thr_scan_kernel(uint32_t* __restrict__ ws, float* __restrict__ s_out, uint32_t k_lo,
+                                                       uint32_t k_hi, float w, float max_value) {
+  typedef thr_digit<PASS> D;
+  constexpr int PER = D::bins / 256;
+  __shared__ uint32_t part[256];
+  __shared__ uint32_t found[4];         // digit_lo, rank_lo', digit_hi, rank_hi'
+  uint32_t* st = ws + (int64_t)blockIdx.x * THR_WORDS;
+  uint32_t* g = st + THR_STATE;
+  const uint32_t pfx[2] = {PASS == 1 ? 0u : st[0], PASS == 1 ? 0u : st[1]};
+  const uint32_t rank[2] = {PASS == 1 ? k_lo : st[2], PASS == 1 ? k_hi : st[3]};
+  const bool two = PASS != 1 && pfx[0] != pfx[1];
+  const int t = threadIdx.x;
+  if (t < 4) found[t] = 0;              // (a histogram that does not hold the rank -- a caller's broken workspace -- gives digit 0)
+  for (int which = 0; which < 2; ++which) {
+    const uint32_t* hist = g + (which == 1 && two ? THR_BINS : 0);
+    uint32_t c[PER], sum = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) { c[j] = hist[t * PER + j]; sum += c[j]; }
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {            // inclusive scan of the 256 partial sums
+      const uint32_t add = t >= d ? part[t - d] : 0u;
+      __syncthreads();
+      part[t] += add;
+      __syncthreads();
+    }
+    uint32_t before = part[t] - sum;               // elements in the bins below this thread's
+    const uint32_t r = rank[which];
+    if (r >= before && r - before < sum) {         // exactly one thread: the counts sum to more than r
+#pragma unroll
+      for (int j = 0; j < PER; ++j) {
+        if (r >= before && r - before < c[j]) {
+          found[2 * which] = (uint32_t)(t * PER + j);
+          found[2 * which + 1] = r - before;
+        }
+        before += c[j];
+      }
+    }
+    __syncthreads();
+  }
+  // the histograms are read: zero them for the next pass (each thread its own bins, which nobody else read)
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    g[t * PER + j] = 0;
+    if (two) g[THR_BINS + t * PER + j] = 0;
+  }
+  if (t == 0) {
+    const uint32_t v_lo = (pfx[0] << (D::prefix_shift - D::shift)) | found[0];
+    const uint32_t v_hi = (pfx[1] << (D::prefix_shift - D::shift)) | found[2];
+    if (PASS < 3) {
+      st[0] = v_lo; st[1] = v_hi; st[2] = found[1]; st[3] = found[3];
+    } else {
+      const float lo = __uint_as_float(v_lo), hi = __uint_as_float(v_hi);
+      const float d = __fsub_rn(hi, lo);
+      const float quant = w < 0.5f ? fmaf(w, d, lo) : fmaf(-d, __fsub_rn(1.0f, w), hi);      // torch.lerp, bit for bit
+      float s = fminf(fmaxf(quant, 1.0f), max_value);
+      if (st[4] != 0 || quant != quant) s = __uint_as_float(0x7fc00000u);       // a NaN in the row: torch.quantile's answer
+      s_out[blockIdx.x] = s;
+    }
+  }
+}
+
+// p0 clamped to +-s and divided by s (IEEE division): the thresholded data prediction
+__device__ __forceinline__ float thr_x0(float x, float e, float sb, float sa, float s) {
+  return __fdiv_rn(clampf(pred_x0(x, e, sb, sa, 0.f), -s, s), s);
+}
+
+// The scales of the (up to) 4 consecutive elements from flat index e on: one division when they share a sample
+__device__ __forceinline__ void thr_scales4(const float* __restrict__ thr, int64_t e, int64_t per, float (&s)[4]) {
+  const int64_t n = e / per, rem = e - n * per;
+  if (rem + 4 <= per) {
+    s[0] = s[1] = s[2] = s[3] = thr[n];
+  } else {                                          // the quad crosses into the next sample(s): per % 4 != 0 only
+    for (int j = 0; j < 4; ++j) s[j] = thr[(e + j) / per];
+  }
+}
+
+// MODE 0: DDPM (prev = c0*x0' + ct*x [+ sigma*z]), a = c0, b = ct, c = sigma;  1: DDIM (prev = sap*x0' + dc*e), a = sap, b = dc
+template <int MODE>
+__device__ __forceinline__ float thr_step_elem(float x, float e, float z, bool add_z, float s, float sb, float sa, float a, float b,
+                                               float c) {
+  const float p0 = thr_x0(x, e, sb, sa, s);
+  if (MODE == 1) return __fadd_rn(__fmul_rn(a, p0), __fmul_rn(b, e));
+  float r = __fadd_rn(__fmul_rn(a, p0), __fmul_rn(b, x));
+  if (add_z) r = __fadd_rn(r, __fmul_rn(c, z));
+  return r;
+}
+
+// One lane = 4 consecutive elements; VEC: every pointer is 16-byte aligned, so they move as one dwordx4 per stream; the last
+// numel % 4 elements take the per-element path, as everything does without VEC.  thr is read at index < numel / per only.
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(256) void thr_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                       const float* __restrict__ nz, const float* __restrict__ thr,
+                                                       float* __restrict__ prev, int64_t numel, int64_t per, float sb, float sa,
+                                                       float a, float b, float c) {
+  const int64_t quads = (numel + 3) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const bool add_z = MODE == 0 && nz != nullptr;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += stride) {
+    const int64_t e = q << 2;
+    if (VEC && e + 4 <= numel) {
+      float s[4];
+      thr_scales4(thr, e, per, s);
+      const float4 xv = *reinterpret_cast<const float4*>(x + e);
+      const float4 ev = *reinterpret_cast<const float4*>(eps + e);
+      float4 zv = make_float4(0.f, 0.f, 0.f, 0.f), r;
+      if (add_z) zv = *reinterpret_cast<const float4*>(nz + e);
+      r.x = thr_step_elem<MODE>(xv.x, ev.x, zv.x, add_z, s[0], sb, sa, a, b, c);
+      r.y = thr_step_elem<MODE>(xv.y, ev.y, zv.y, add_z, s[1], sb, sa, a, b, c);
+      r.z = thr_step_elem<MODE>(xv.z, ev.z, zv.z, add_z, s[2], sb, sa, a, b, c);
+      r.w = thr_step_elem<MODE>(xv.w, ev.w, zv.w, add_z, s[3], sb, sa, a, b, c);
+      *reinterpret_cast<float4*>(prev + e) = r;
+    } else {
+      for (int j = 0; j < 4 && e + j < numel; ++j) {
+        const int64_t i = e + j;
+        prev[i] = thr_step_elem<MODE>(x[i], eps[i], add_z ? nz[i] : 0.f, add_z, thr[i / per], sb, sa, a, b, c);
+      }
+    }
+  }
+}
+
 // (x/2 + 0.5).clamp(0,1), NCHW -> NHWC.  grid = (ceil(hw/256), n)
 template <int MODE>
 __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restrict__ x, void* __restrict__ out, int c,
@@ -471,7 +703,119 @@ DSG_API int dsg_add_noise_philox(const float* x0, const float* sqrt_a, const flo
 
 namespace dsg {
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// do [a, a + abytes) and [b, b + bbytes) share a byte?  (NULL overlaps nothing)
+static inline bool overlaps2(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
+  if (!a || !b) return false;
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y ? y - x < abytes : x - y < bbytes;
+}
+
+template <int PASS>
+static void thr_pass(const float* x, const float* e, uint32_t* ws, float* s, int32_t n, int64_t per, float sb, float sa,
+                     uint32_t k_lo, uint32_t k_hi, float w, float max_value, bool vec, hipStream_t st) {
+  // enough blocks per sample to fill the chip at any batch, never more than the sample has 1024-element chunks
+  int64_t bps = cdiv64(per, 1024), cap = cdiv64(2048, n);
+  if (bps > cap) bps = cap;
+  const dim3 grid((unsigned)bps, (unsigned)n), block(256);
+  if (vec) hipLaunchKernelGGL((thr_hist_kernel<PASS, true>), grid, block, 0, st, x, e, ws, per, sb, sa);
+  else hipLaunchKernelGGL((thr_hist_kernel<PASS, false>), grid, block, 0, st, x, e, ws, per, sb, sa);
+  hipLaunchKernelGGL((thr_scan_kernel<PASS>), dim3((unsigned)n), block, 0, st, ws, s, k_lo, k_hi, w, max_value);
+}
 }  // namespace dsg
+
+DSG_API int dsg_dynthresh_workspace_bytes(int32_t n, size_t* bytes) {
+  DSG_CHECK_ARG(bytes, "dsg_dynthresh_workspace_bytes: NULL pointer");
+  DSG_CHECK_ARG(n > 0 && n <= 65535, "dsg_dynthresh_workspace_bytes: n=%d outside [1, 65535]", n);
+  *bytes = (size_t)n * dsg::THR_WORDS * sizeof(uint32_t);
+  return DSG_OK;
+}
+
+DSG_API int dsg_dynthresh_scale(const float* sample, const float* eps, float* s, int32_t n, int64_t per_sample,
+                                float sqrt_beta_prod_t, float sqrt_alpha_prod_t, int64_t k_lo, int64_t k_hi, float w,
+                                float sample_max_value, void* workspace, size_t workspace_bytes, void* stream) {
+  DSG_CHECK_ARG(sample && eps && s && workspace, "dsg_dynthresh_scale: NULL pointer");
+  DSG_CHECK_ARG(n > 0 && n <= 65535, "dsg_dynthresh_scale: n=%d outside [1, 65535]", n);
+  DSG_CHECK_ARG(per_sample > 0 && per_sample <= 0x7fffffff, "dsg_dynthresh_scale: per_sample=%lld outside [1, 2^31 - 1]",
+                (long long)per_sample);
+  DSG_CHECK_ARG(k_lo >= 0 && k_lo < per_sample && k_hi >= 0 && k_hi < per_sample,
+                "dsg_dynthresh_scale: rank k_lo=%lld / k_hi=%lld outside [0, per_sample=%lld)", (long long)k_lo, (long long)k_hi,
+                (long long)per_sample);
+  DSG_CHECK_ARG(k_hi == k_lo || k_hi == k_lo + 1, "dsg_dynthresh_scale: rank k_hi=%lld is neither k_lo=%lld nor k_lo + 1",
+                (long long)k_hi, (long long)k_lo);
+  DSG_CHECK_ARG(w >= 0.f && w < 1.f, "dsg_dynthresh_scale: interpolation weight w=%g outside [0, 1)", (double)w);
+  DSG_CHECK_ARG(sample_max_value >= 1.f, "dsg_dynthresh_scale: sample_max_value=%g below 1", (double)sample_max_value);
+  const size_t need = (size_t)n * dsg::THR_WORDS * sizeof(uint32_t);
+  if (workspace_bytes < need)
+    return dsg::fail(DSG_ERR_WORKSPACE_TOO_SMALL, "dsg_dynthresh_scale: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  DSG_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 3u) == 0, "dsg_dynthresh_scale: workspace is not 4-byte aligned");
+  const uint64_t in_bytes = (uint64_t)n * (uint64_t)per_sample * sizeof(float), s_bytes = (uint64_t)n * sizeof(float);
+  const void* ins[2] = {sample, eps};
+  for (int i = 0; i < 2; ++i) {
+    DSG_CHECK_ARG(!dsg::overlaps2(s, s_bytes, ins[i], in_bytes), "dsg_dynthresh_scale: s overlaps an input (input %d)", i);
+    DSG_CHECK_ARG(!dsg::overlaps2(workspace, need, ins[i], in_bytes), "dsg_dynthresh_scale: the workspace overlaps an input (input %d)", i);
+  }
+  DSG_CHECK_ARG(!dsg::overlaps2(workspace, need, s, s_bytes), "dsg_dynthresh_scale: the workspace overlaps s");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  uint32_t* ws = static_cast<uint32_t*>(workspace);
+  DSG_HIP(dsg::zero_words(ws, (size_t)n * dsg::THR_WORDS, st));
+  // dwordx4 loads need every sample's first element on a 16-byte boundary
+  const bool vec = (per_sample & 3) == 0 && dsg::aligned16(sample) && dsg::aligned16(eps);
+  const uint32_t lo = (uint32_t)k_lo, hi = (uint32_t)k_hi;
+  dsg::thr_pass<1>(sample, eps, ws, s, n, per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, lo, hi, w, sample_max_value, vec, st);
+  dsg::thr_pass<2>(sample, eps, ws, s, n, per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, lo, hi, w, sample_max_value, vec, st);
+  dsg::thr_pass<3>(sample, eps, ws, s, n, per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, lo, hi, w, sample_max_value, vec, st);
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
+
+namespace dsg {
+static int thr_step_check(const char* who, const float* sample, const float* eps, const float* thr, const float* prev,
+                          int64_t numel, int64_t per) {
+  if (!(sample && eps && thr && prev)) return fail(DSG_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  if (numel <= 0) return fail(DSG_ERR_INVALID_ARG, "%s: numel must be positive", who);
+  if (per <= 0 || numel % per != 0)
+    return fail(DSG_ERR_INVALID_ARG, "%s: per_sample=%lld does not divide numel=%lld", who, (long long)per, (long long)numel);
+  if (overlaps2(prev, (uint64_t)numel * sizeof(float), thr, (uint64_t)(numel / per) * sizeof(float)))
+    return fail(DSG_ERR_INVALID_ARG, "%s: prev overlaps thr", who);
+  return DSG_OK;
+}
+}  // namespace dsg
+
+DSG_API int dsg_ddpm_step_thr(const float* sample, const float* eps, const float* noise, const float* thr, float* prev,
+                              int64_t numel, int64_t per_sample, float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float coef_x0,
+                              float coef_xt, float sigma, void* stream) {
+  const int rc = dsg::thr_step_check("dsg_ddpm_step_thr", sample, eps, thr, prev, numel, per_sample);
+  if (rc != DSG_OK) return rc;
+  const bool vec = dsg::aligned16(sample) && dsg::aligned16(eps) && dsg::aligned16(noise) && dsg::aligned16(prev);
+  const dim3 grid(dsg::philox_blocks(numel)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (vec)
+    hipLaunchKernelGGL((dsg::thr_step_kernel<0, true>), grid, block, 0, st, sample, eps, noise, thr, prev, numel, per_sample,
+                       sqrt_beta_prod_t, sqrt_alpha_prod_t, coef_x0, coef_xt, sigma);
+  else
+    hipLaunchKernelGGL((dsg::thr_step_kernel<0, false>), grid, block, 0, st, sample, eps, noise, thr, prev, numel, per_sample,
+                       sqrt_beta_prod_t, sqrt_alpha_prod_t, coef_x0, coef_xt, sigma);
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
+
+DSG_API int dsg_ddim_step_thr(const float* sample, const float* eps, const float* thr, float* prev, int64_t numel,
+                              int64_t per_sample, float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float sqrt_alpha_prev,
+                              float dir_coef, void* stream) {
+  const int rc = dsg::thr_step_check("dsg_ddim_step_thr", sample, eps, thr, prev, numel, per_sample);
+  if (rc != DSG_OK) return rc;
+  const bool vec = dsg::aligned16(sample) && dsg::aligned16(eps) && dsg::aligned16(prev);
+  const dim3 grid(dsg::philox_blocks(numel)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (vec)
+    hipLaunchKernelGGL((dsg::thr_step_kernel<1, true>), grid, block, 0, st, sample, eps, (const float*)nullptr, thr, prev, numel,
+                       per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, sqrt_alpha_prev, dir_coef, 0.f);
+  else
+    hipLaunchKernelGGL((dsg::thr_step_kernel<1, false>), grid, block, 0, st, sample, eps, (const float*)nullptr, thr, prev, numel,
+                       per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, sqrt_alpha_prev, dir_coef, 0.f);
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
 
 DSG_API int dsg_repaint_step(const dsg_repaint_step_args* a, void* stream) {
   DSG_CHECK_ARG(a, "dsg_repaint_step: NULL args");

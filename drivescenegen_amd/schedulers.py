@@ -11,7 +11,7 @@ Formulas: SURVEY.md App. A.3 / A.3b.
 Host side (this file): the beta / alpha-bar tables, the integer timestep tables and the per-step fp32
 scalars, computed with the same fp32 operation order as the reference so they are bit-identical.
 Device side: the elementwise tensor math, in libdsg.so (dsg_add_noise / dsg_ddpm_step / dsg_ddim_step / dsg_repaint_step /
-dsg_repaint_undo / dsg_dpmsolver_step).
+dsg_repaint_undo / dsg_dpmsolver_step; with ``thresholding=True``: dsg_dynthresh_scale + dsg_ddpm_step_thr / dsg_ddim_step_thr).
 """
 from __future__ import annotations
 
@@ -74,7 +74,7 @@ class DDPMScheduler:
                      thresholding=False, dynamic_thresholding_ratio=0.995, clip_sample_range=1.0,
                      sample_max_value=1.0, timestep_spacing="leading", steps_offset=0)
     # config keys this engine runs at their default value only
-    _fixed_keys = ("beta_schedule", "trained_betas", "prediction_type", "thresholding", "timestep_spacing")
+    _fixed_keys = ("beta_schedule", "trained_betas", "prediction_type", "timestep_spacing")
 
     def __init__(self, **kwargs):
         cfg = dict(self._defaults)
@@ -87,6 +87,7 @@ class DDPMScheduler:
                 raise NotImplementedError(f"{self._class_name}: {key}={cfg[key]!r} is outside the DriveSceneGen "
                                           f"path (supported: {self._defaults[key]!r})")
         self._check_extra(cfg)
+        self._check_thresholding(cfg)
         self.config = FrozenConfig(**cfg)
         n = cfg["num_train_timesteps"]
         self.betas = torch.linspace(cfg["beta_start"], cfg["beta_end"], n, dtype=torch.float32)
@@ -99,10 +100,26 @@ class DDPMScheduler:
         self.timesteps = torch.from_numpy(np.arange(0, n)[::-1].copy())
         self._dev_tables = {}
         self._scalar_cache = {}
+        self._rank_cache = {}           # (per, q) -> (k_lo, k_hi, w) of the thresholding quantile
+        self._thr_buffers = {}          # (device, n) -> (workspace, workspace bytes, s [n])
 
     def _check_extra(self, cfg):
         if cfg["variance_type"] != "fixed_small":
             raise NotImplementedError("DDPMScheduler: only variance_type='fixed_small' (the reference default)")
+
+    def _check_thresholding(self, cfg):
+        """Dynamic thresholding (diffusers' ``thresholding`` / ``dynamic_thresholding_ratio`` / ``sample_max_value``) where the
+        class runs it: DDPMScheduler and DDIMScheduler.  A class that keeps ``thresholding`` in ``_fixed_keys`` or has no such
+        key has refused already."""
+        if "thresholding" not in cfg or "thresholding" in self._fixed_keys:
+            return
+        if not isinstance(cfg["thresholding"], (bool, np.bool_)):
+            raise ValueError(f"{self._class_name}: thresholding={cfg['thresholding']!r} is not a bool")
+        q, m = cfg["dynamic_thresholding_ratio"], cfg["sample_max_value"]
+        if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 <= q <= 1.0:
+            raise ValueError(f"{self._class_name}: dynamic_thresholding_ratio={q!r} is outside [0, 1]")
+        if isinstance(m, bool) or not isinstance(m, (int, float, np.integer, np.floating)) or not 1.0 <= m < float("inf"):
+            raise ValueError(f"{self._class_name}: sample_max_value={m!r} is not a finite number >= 1")
 
     # training_pipeline.py:76 reads this attribute directly
     @property
@@ -206,6 +223,51 @@ class DDPMScheduler:
         return dict(sqrt_beta_prod_t=float(b_t ** 0.5), sqrt_alpha_prod_t=float(a_t ** 0.5), coef_x0=float(c0),
                     coef_xt=float(ct), sigma=float(var ** 0.5))
 
+    # ---- dynamic thresholding ---------------------------------------------------------------------
+    def threshold_ranks(self, per: int):
+        """(k_lo, k_hi, w) of the ``dynamic_thresholding_ratio`` quantile of `per` values, as torch.quantile forms them: the
+        rank is the fp32 product q * (per - 1).  Memoised per (per, q)."""
+        key = (int(per), float(self.config.dynamic_thresholding_ratio))
+        hit = self._rank_cache.get(key)
+        if hit is None:
+            rank = np.float32(key[1]) * np.float32(per - 1)
+            k_lo = int(np.floor(rank))
+            # (per - 1 above 2^24 may round UP on its way to fp32: no rank leaves the sample)
+            k_lo = min(k_lo, per - 1)
+            k_hi = min(int(np.ceil(rank)), per - 1)
+            w = float(rank - np.float32(k_lo)) if k_hi > k_lo else 0.0
+            hit = self._rank_cache[key] = (k_lo, k_hi, w)
+        return hit
+
+    def _threshold_scale(self, x, e, s):
+        """The per-sample scale of the thresholded data prediction, device fp32 [N] (``dsg_dynthresh_scale``; include/dsg.h).
+        The workspace and the result live in buffers cached per (device, N): the result is consumed by the step kernel
+        enqueued right behind, on the same stream."""
+        n = int(x.shape[0])
+        per = x.numel() // n
+        lib = _lib.load()
+        key = (str(x.device), n)
+        buf = self._thr_buffers.get(key)
+        if buf is None:
+            import ctypes
+            nbytes = ctypes.c_size_t()
+            _lib.check(lib.dsg_dynthresh_workspace_bytes(n, ctypes.byref(nbytes)))
+            buf = self._thr_buffers[key] = (torch.empty(nbytes.value, dtype=torch.uint8, device=x.device), nbytes.value,
+                                            torch.empty(n, dtype=torch.float32, device=x.device))
+        ws, ws_bytes, scale = buf
+        k_lo, k_hi, w = self.threshold_ranks(per)
+        _lib.check(lib.dsg_dynthresh_scale(_lib.ptr(x), _lib.ptr(e), _lib.ptr(scale), n, per, s["sqrt_beta_prod_t"],
+                                           s["sqrt_alpha_prod_t"], k_lo, k_hi, w, float(self.config.sample_max_value),
+                                           _lib.ptr(ws), ws_bytes, _lib.stream_ptr(x.device)))
+        return scale, per
+
+    @staticmethod
+    def _check_thresholded_inputs(who, sample, model_output):
+        if sample.dim() < 2 or sample.numel() == 0 or sample.dtype != torch.float32 or model_output.dtype != torch.float32:
+            raise ValueError(f"{who}: thresholding needs a non-empty fp32 [N, ...] sample")
+        if tuple(model_output.shape) != tuple(sample.shape):
+            raise ValueError(f"{who}: model output {tuple(model_output.shape)} != sample {tuple(sample.shape)}")
+
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, variance_noise=None):
         if not sample.is_cuda:
             raise RuntimeError("DDPMScheduler.step runs on the MI355X HIP engine only (got a CPU tensor)")
@@ -227,9 +289,16 @@ class DDPMScheduler:
         prev = torch.empty_like(x)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dsg_ddpm_step(_lib.ptr(x), _lib.ptr(e), nptr, _lib.ptr(prev), x.numel(),
-                                                s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"], clip, s["coef_x0"],
-                                                s["coef_xt"], s["sigma"], _lib.stream_ptr(x.device)))
+            if self.config.thresholding:        # (takes precedence over clip_sample, as in diffusers)
+                self._check_thresholded_inputs("DDPMScheduler.step", x, e)
+                scale, per = self._threshold_scale(x, e, s)
+                _lib.check(_lib.load().dsg_ddpm_step_thr(_lib.ptr(x), _lib.ptr(e), nptr, _lib.ptr(scale), _lib.ptr(prev),
+                                                        x.numel(), per, s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"],
+                                                        s["coef_x0"], s["coef_xt"], s["sigma"], _lib.stream_ptr(x.device)))
+            else:
+                _lib.check(_lib.load().dsg_ddpm_step(_lib.ptr(x), _lib.ptr(e), nptr, _lib.ptr(prev), x.numel(),
+                                                    s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"], clip, s["coef_x0"],
+                                                    s["coef_xt"], s["sigma"], _lib.stream_ptr(x.device)))
             if host is not None:
                 host.consumed = torch.cuda.Event()
                 host.consumed.record(torch.cuda.current_stream(x.device))
@@ -311,9 +380,16 @@ class DDIMScheduler(DDPMScheduler):
         prev = torch.empty_like(x)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().dsg_ddim_step(_lib.ptr(x), _lib.ptr(e), _lib.ptr(prev), x.numel(),
-                                                s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"], clip,
-                                                s["sqrt_alpha_prev"], s["dir_coef"], _lib.stream_ptr(x.device)))
+            if self.config.thresholding:        # (takes precedence over clip_sample, as in diffusers)
+                self._check_thresholded_inputs("DDIMScheduler.step", x, e)
+                scale, per = self._threshold_scale(x, e, s)
+                _lib.check(_lib.load().dsg_ddim_step_thr(_lib.ptr(x), _lib.ptr(e), _lib.ptr(scale), _lib.ptr(prev), x.numel(),
+                                                        per, s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"],
+                                                        s["sqrt_alpha_prev"], s["dir_coef"], _lib.stream_ptr(x.device)))
+            else:
+                _lib.check(_lib.load().dsg_ddim_step(_lib.ptr(x), _lib.ptr(e), _lib.ptr(prev), x.numel(),
+                                                    s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"], clip,
+                                                    s["sqrt_alpha_prev"], s["dir_coef"], _lib.stream_ptr(x.device)))
         if eta > 0:
             z = variance_noise if variance_noise is not None else _randn_like_reference(
                 model_output.shape, generator, model_output.device, model_output.dtype)
@@ -384,6 +460,8 @@ class RePaintScheduler(DDIMScheduler, _NoiseSource):
     _class_name = "RePaintScheduler"
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", eta=0.0,
                      trained_betas=None, clip_sample=True)
+    # (diffusers' RePaintScheduler has no thresholding keys: passing one is an unexpected argument, and its step never thresholds)
+    _fixed_keys = ("beta_schedule", "trained_betas")
 
     def _check_extra(self, cfg):
         pass
@@ -551,7 +629,8 @@ class DPMSolverMultistepScheduler(DDPMScheduler, _NoiseSource):
     is the Philox tensor (seed, offset + k), generated inside the step kernel.
 
     Not built (raising): Karras sigmas, dynamic thresholding, the noise-prediction forms "dpmsolver" / "sde-dpmsolver",
-    v-prediction, learned variances.  ``variance_type`` "fixed_small" / "fixed_large" (what a converted DDPM config carries) are
+    v-prediction, learned variances.  ``from_config`` of a DDPM / DDIM config with ``thresholding=True`` (or another ratio or
+    maximum) therefore raises too; ``dsg_dynthresh_scale`` already takes this solver's (sigma_s, alpha_s).  ``variance_type`` "fixed_small" / "fixed_large" (what a converted DDPM config carries) are
     accepted: as in diffusers, only the learned forms would change this scheduler's arithmetic."""
 
     _class_name = "DPMSolverMultistepScheduler"

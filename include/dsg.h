@@ -359,6 +359,45 @@ int dsg_ddpm_step(const float* sample, const float* eps, const float* noise /* N
 int dsg_ddim_step(const float* sample, const float* eps, float* prev, int64_t numel,
                   float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float clip, float sqrt_alpha_prev,
                   float dir_coef, void* stream);
+/* Dynamic thresholding (Saharia et al., "Imagen", 2022, section 2.3; diffusers 0.20.0 `thresholding=True`, `_threshold_sample`):
+ * the data prediction of a step is limited per SAMPLE by a quantile of its own magnitudes instead of the static +-clip.
+ * The arithmetic is pinned bit for bit (tests/dynthresh_oracle.py restates it, tests/test_gpu_dynthresh.py checks it): all
+ * operations fp32 and each rounded on its own, except the two fmaf.  Per sample n, per = per_sample elements:
+ *     p0[i]  = (x[i] - sqrt_beta_prod_t*e[i]) / sqrt_alpha_prod_t          the p0 of dsg_ddpm_step / dsg_ddim_step, unclipped
+ *     a[i]   = |p0[i]|
+ *     rank   = fp32(q) * fp32(per - 1)                                      HOST: an fp32 product
+ *     k_lo   = floor(rank);  k_hi = ceil(rank);  w = rank - fp32(k_lo)
+ *     v_lo, v_hi = the k_lo-th and k_hi-th smallest of a[.]                 0-based, exact
+ *     d      = v_hi - v_lo
+ *     quant  = w < 0.5 ? fmaf(w, d, v_lo) : fmaf(-d, 1 - w, v_hi)           torch.quantile's interpolation
+ *     s[n]   = min(max(quant, 1), sample_max_value)                         NaN when a[.] holds a NaN (torch's answer)
+ *     x0'[i] = min(max(p0[i], -s[n]), s[n]) / s[n]                          IEEE division
+ *     DDPM:  prev = coef_x0*x0' + coef_xt*x  (+ sigma*z when noise != NULL)     dsg_ddpm_step's operation order
+ *     DDIM:  prev = sqrt_alpha_prev*x0' + dir_coef*e                            (eps is not recomputed: diffusers 0.20.0)
+ * dsg_dynthresh_scale writes s (device fp32 [n]).  It takes the two scalars of ANY data prediction m0 = (x - sigma*e) / alpha
+ * (dsg_dpmsolver_step's too) and never stores p0: an exact MSB-first radix select on the bit pattern of |p0| in three histogram
+ * passes (11 + 11 + 9 bits), each followed by a one-block-per-sample scan that picks the bin of BOTH ranks; 1 + 6 launches, the
+ * inputs read three times, integer atomics only: the result is bitwise reproducible.  The select state lives in `workspace`
+ * (dsg_dynthresh_workspace_bytes(n); caller-owned, contents undefined before and after, zeroed here by a kernel): no readback,
+ * no allocation, no synchronisation, legal under stream capture.  No loop depends on the data: NaN / Inf inputs end normally, a
+ * row holding a NaN gets s = NaN (and a NaN `prev` row from the step), other rows are unaffected.
+ * Checked before any HIP call: NULL pointers, n outside [1, 65535], per_sample outside [1, 2^31 - 1], a rank outside
+ * [0, per_sample) or k_hi not in {k_lo, k_lo + 1}, w outside [0, 1), sample_max_value < 1, a workspace too small
+ * (DSG_ERR_WORKSPACE_TOO_SMALL) or misaligned, `s` or the workspace overlapping an input or each other.
+ * dsg_ddpm_step_thr / dsg_ddim_step_thr: the step with s in place of the clip (`thr` = s, device [numel / per_sample]; `noise` as
+ * in dsg_ddpm_step: device or pinned host memory, NULL when t == 0).  All pointers 16-byte aligned: dwordx4 accesses (the last
+ * numel % 4 elements singly); otherwise dword accesses.  Checked: NULL pointers, numel <= 0, per_sample not dividing numel,
+ * `prev` overlapping `thr`. */
+int dsg_dynthresh_workspace_bytes(int32_t n, size_t* bytes);
+int dsg_dynthresh_scale(const float* sample, const float* eps, float* s /* device [n] */, int32_t n, int64_t per_sample,
+                        float sqrt_beta_prod_t, float sqrt_alpha_prod_t, int64_t k_lo, int64_t k_hi, float w,
+                        float sample_max_value, void* workspace, size_t workspace_bytes, void* stream);
+int dsg_ddpm_step_thr(const float* sample, const float* eps, const float* noise /* NULL when t == 0 */,
+                      const float* thr /* device [numel / per_sample] */, float* prev, int64_t numel, int64_t per_sample,
+                      float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float coef_x0, float coef_xt, float sigma, void* stream);
+int dsg_ddim_step_thr(const float* sample, const float* eps, const float* thr /* device [numel / per_sample] */, float* prev,
+                      int64_t numel, int64_t per_sample, float sqrt_beta_prod_t, float sqrt_alpha_prod_t,
+                      float sqrt_alpha_prev, float dir_coef, void* stream);
 /* Device address of a pinned host buffer, for the kernels that read host memory in place (dsg_ddpm_step's `noise`).  Host-only. */
 int dsg_host_device_pointer(const void* host, void** device);
 /* Counter-based device noise: Philox4x32-10 + Box-Muller (opt-in; the default training loop keeps the reference's host draw).
