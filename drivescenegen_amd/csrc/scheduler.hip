@@ -3,9 +3,16 @@
 // Replaces the tensor arithmetic of diffusers' DDPMScheduler.add_noise / .step and
 // DDIMScheduler.step (reference call sites: DriveSceneGen/pipeline/training_pipeline.py:80
 // `noise_scheduler.add_noise`, and the DDPMPipeline loop behind training_pipeline.py:26-32 and
-// DriveSceneGen/scripts/generation.py:14-20; formulas SURVEY.md App. A.3 / A.3b / A.4).
+// DriveSceneGen/scripts/generation.py:14-20; formulas SURVEY.md App. A.3 / A.3b / A.4), and adds the samplers diffusers ships
+// next to them: RePaint, DPM-Solver++ multistep, dynamic thresholding.
 // Every expression is evaluated with individually rounded fp32 operations in the reference's
 // order (fma contraction disabled for this file, IEEE division), so results are bit-identical to torch-CPU.
+//
+// The file reads: per-element formulas (each operation order stated ONCE) -> the training / headline kernels (add_noise, philox,
+// ddpm_step, ddim_step: one loop each, untouched by the sampler features) -> the quad skeleton ("one lane owns four consecutive
+// elements") and the four sampler kernels built on it -> the thresholding quantile -> postprocess -> host helpers -> entry points.
+#include <type_traits>
+
 #include "dsg_common.h"
 
 // HIP's __fmul_rn/__fadd_rn are plain operators (contractible); forbid fma contraction for this TU instead.
@@ -14,6 +21,35 @@
 namespace dsg {
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The per-element formulas.  Every kernel below that needs one calls it here, so each operation order exists once.
+// a*x + b*z: two multiplies, one add (add_noise; RePaint's undo and its known / unknown blend)
+__device__ __forceinline__ float axpby(float a, float x, float b, float z) {
+  return __fadd_rn(__fmul_rn(a, x), __fmul_rn(b, z));
+}
+
+// r + c*z: one more term of a sum taken left to right (a noise term; DPM-Solver's higher-order terms)
+__device__ __forceinline__ float add_scaled(float r, float c, float z) { return __fadd_rn(r, __fmul_rn(c, z)); }
+
+// the data prediction p0 = (x - sb*e) / sa, clamped to +-clip when clip > 0
+__device__ __forceinline__ float pred_x0(float x, float e, float sb, float sa, float clip) {
+  float v = __fdiv_rn(__fsub_rn(x, __fmul_rn(sb, e)), sa);
+  if (clip > 0.f) v = clampf(v, -clip, clip);
+  return v;
+}
+
+// p0 clamped to +-s and divided by s (IEEE division): the thresholded data prediction
+__device__ __forceinline__ float thr_x0(float x, float e, float sb, float sa, float s) {
+  return __fdiv_rn(clampf(pred_x0(x, e, sb, sa, 0.f), -s, s), s);
+}
+
+// DDPM: prev = c0*p0 + ct*x, then [+ sigma*z] where the step has a noise term
+__device__ __forceinline__ float ddpm_combine(float p0, float x, float c0, float ct) { return axpby(c0, p0, ct, x); }
+__device__ __forceinline__ float ddpm_add_noise(float r, float sigma, float z) { return add_scaled(r, sigma, z); }
+
+// DDIM: prev = sap*p0 + dc*e
+__device__ __forceinline__ float ddim_combine(float p0, float e, float sap, float dc) { return axpby(sap, p0, dc, e); }
 
 // grid = (ceil(per_sample/1024), n)
 __global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict__ x0, const float* __restrict__ nz,
@@ -28,14 +64,13 @@ __global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict_
     const float4 x = *reinterpret_cast<const float4*>(x0 + base + i0);
     const float4 e = *reinterpret_cast<const float4*>(nz + base + i0);
     float4 r;
-    r.x = __fadd_rn(__fmul_rn(a, x.x), __fmul_rn(b, e.x));
-    r.y = __fadd_rn(__fmul_rn(a, x.y), __fmul_rn(b, e.y));
-    r.z = __fadd_rn(__fmul_rn(a, x.z), __fmul_rn(b, e.z));
-    r.w = __fadd_rn(__fmul_rn(a, x.w), __fmul_rn(b, e.w));
+    r.x = axpby(a, x.x, b, e.x);
+    r.y = axpby(a, x.y, b, e.y);
+    r.z = axpby(a, x.z, b, e.z);
+    r.w = axpby(a, x.w, b, e.w);
     *reinterpret_cast<float4*>(out + base + i0) = r;
   } else {
-    for (int k = 0; k < 4 && i0 + k < per; ++k)
-      out[base + i0 + k] = __fadd_rn(__fmul_rn(a, x0[base + i0 + k]), __fmul_rn(b, nz[base + i0 + k]));
+    for (int k = 0; k < 4 && i0 + k < per; ++k) out[base + i0 + k] = axpby(a, x0[base + i0 + k], b, nz[base + i0 + k]);
   }
 }
 
@@ -111,10 +146,10 @@ __global__ __launch_bounds__(256) void philox_kernel(const float* __restrict__ x
         const float a = sa[n], b = sb[n];
         const float4 x = *reinterpret_cast<const float4*>(x0 + e);
         float4 q;
-        q.x = __fadd_rn(__fmul_rn(a, x.x), __fmul_rn(b, z[0]));
-        q.y = __fadd_rn(__fmul_rn(a, x.y), __fmul_rn(b, z[1]));
-        q.z = __fadd_rn(__fmul_rn(a, x.z), __fmul_rn(b, z[2]));
-        q.w = __fadd_rn(__fmul_rn(a, x.w), __fmul_rn(b, z[3]));
+        q.x = axpby(a, x.x, b, z[0]);
+        q.y = axpby(a, x.y, b, z[1]);
+        q.z = axpby(a, x.z, b, z[2]);
+        q.w = axpby(a, x.w, b, z[3]);
         *reinterpret_cast<float4*>(noisy + e) = q;
       }
     } else {
@@ -122,17 +157,11 @@ __global__ __launch_bounds__(256) void philox_kernel(const float* __restrict__ x
         o[e + k] = z[k];
         if (MODE == 2) {
           const int64_t n = (e + k) / per;
-          noisy[e + k] = __fadd_rn(__fmul_rn(sa[n], x0[e + k]), __fmul_rn(sb[n], z[k]));
+          noisy[e + k] = axpby(sa[n], x0[e + k], sb[n], z[k]);
         }
       }
     }
   }
-}
-
-__device__ __forceinline__ float pred_x0(float x, float e, float sb, float sa, float clip) {
-  float v = __fdiv_rn(__fsub_rn(x, __fmul_rn(sb, e)), sa);
-  if (clip > 0.f) v = clampf(v, -clip, clip);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
@@ -143,8 +172,8 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict_
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += stride) {
     const float xv = x[i];
     const float p0 = pred_x0(xv, eps[i], sb, sa, clip);
-    float r = __fadd_rn(__fmul_rn(c0, p0), __fmul_rn(ct, xv));
-    if (nz) r = __fadd_rn(r, __fmul_rn(sigma, nz[i]));
+    float r = ddpm_combine(p0, xv, c0, ct);
+    if (nz) r = ddpm_add_noise(r, sigma, nz[i]);
     prev[i] = r;
   }
 }
@@ -155,126 +184,155 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict_
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < numel; i += stride) {
     const float e = eps[i];
-    const float p0 = pred_x0(x[i], e, sb, sa, clip);
-    prev[i] = __fadd_rn(__fmul_rn(sap, p0), __fmul_rn(dc, e));
+    prev[i] = ddim_combine(pred_x0(x[i], e, sb, sa, clip), e, sap, dc);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The quad skeleton of the sampler kernels (repaint_step, repaint_undo, dpmsolver_step, thr_step).  One lane owns one QUAD:
+// the 4 consecutive elements [4q, 4q + 4) of the flat tensor, which are also one Philox block (the mapping above), so a step's
+// noise can be made where it is consumed.  A kernel is
+//   for_each_quad(numel, [&](q, e) { vec = quad_is_vec<VEC>(e, numel); load4 ...; noise4<NOISE> ...; arithmetic; store4 ...; })
+// ONE vector rule for all of them: a launch is VEC when the host found every pointer it touches 16-byte aligned; inside a VEC
+// launch a WHOLE quad (e + 4 <= numel) moves as one dwordx4 per stream; the last numel % 4 elements, and everything in a launch
+// that is not VEC, take the per-element path.  Elements of a quad past numel are loaded as 0, computed and never stored.
+enum { NOISE_NONE = 0, NOISE_READ = 1, NOISE_PHILOX = 2 };     // no noise term | read from `nz` | this lane's Philox block
+
+struct philox_words {                                          // (seed, offset) as the kernels take them
+  uint32_t seed_lo, seed_hi, off_lo, off_hi;
+  static philox_words of(uint64_t seed, uint64_t offset) {
+    return {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
+  }
+};
+
+template <class F>
+__device__ __forceinline__ void for_each_quad(int64_t numel, F&& body) {
+  const int64_t quads = (numel + 3) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += stride) body(q, q << 2);
+}
+
+template <bool VEC>
+__device__ __forceinline__ bool quad_is_vec(int64_t e, int64_t numel) { return VEC && e + 4 <= numel; }
+
+__device__ __forceinline__ void load4(const float* __restrict__ p, int64_t e, int64_t numel, bool vec, float (&v)[4]) {
+  if (vec) {
+    const float4 t = *reinterpret_cast<const float4*>(p + e);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    for (int k = 0; k < 4; ++k) v[k] = e + k < numel ? p[e + k] : 0.f;
+  }
+}
+
+__device__ __forceinline__ void store4(float* __restrict__ p, int64_t e, int64_t numel, bool vec, const float (&v)[4]) {
+  if (vec) {
+    *reinterpret_cast<float4*>(p + e) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int k = 0; k < 4 && e + k < numel; ++k) p[e + k] = v[k];
+  }
+}
+
+// the noise of quad q; echoed to `noise_out` when the caller wants the tensor the step used
+template <int NOISE>
+__device__ __forceinline__ void noise4(const float* __restrict__ nz, float* __restrict__ noise_out, int64_t q, int64_t numel,
+                                       bool vec, const philox_words& w, float (&z)[4]) {
+  if (NOISE == NOISE_NONE) {
+    z[0] = z[1] = z[2] = z[3] = 0.f;
+    return;
+  }
+  if (NOISE == NOISE_READ) {
+    load4(nz, q << 2, numel, vec, z);
+  } else {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)q, (uint32_t)((uint64_t)q >> 32), w.off_lo, w.off_hi, w.seed_lo, w.seed_hi, r);
+    box_muller(r[0], r[1], z[0], z[1]);
+    box_muller(r[2], r[3], z[2], z[3]);
+  }
+  if (noise_out) store4(noise_out, q << 2, numel, vec, z);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // RePaint (Lugmayr et al., CVPR 2022, Algorithm 1; diffusers' RePaintScheduler.step / .undo_step): scene completion with an
 // unconditional network.  One pass per reverse step, per element and in THIS order (include/dsg.h states it as the contract):
-//   p0      = (x - sb*e) / sa, clamped to +-clip when clip > 0                 (pred_x0 above)
-//   unknown = sap*p0 + dc*e     [+ std*z  when add_std]
+//   p0      = (x - sb*e) / sa, clamped to +-clip when clip > 0                 (pred_x0)
+//   unknown = sap*p0 + dc*e     [+ std*z  when add_std]                        (ddim_combine, add_scaled)
 //   known   = sap*orig + sbp*z
 //   prev    = m*known + (1 - m)*unknown
-// z is ONE noise value per element, used in both places: read from `nz` (device memory or a pinned host buffer, SRC 0) or made
-// here from the Philox stream above (SRC 1: element e = lane e % 4 of block e / 4, dsg_philox_normal's mapping).  Each lane
-// owns one Philox block = 4 consecutive elements; with hw % 4 == 0 and 16-byte aligned pointers (VEC) those share (n, c), so
-// every stream is one dwordx4 access and `orig` / `m` are addressed through their batch / channel strides (0 = broadcast).
+// z is ONE noise value per element, used in both places (NOISE_READ: device memory or a pinned host buffer; NOISE_PHILOX).
+// `orig` / `m` are addressed through their batch / channel strides (0 = broadcast).
 struct repaint_geom {
   int64_t numel, chw, hw;
   int64_t orig_sn;          // 0 (one original for the batch) or chw
   int64_t m_sn, m_sc;       // mask strides over n and c: 0 where its extent is 1
+  // where flat element i of the sample finds its original and its mask weight
+  __device__ __forceinline__ void locate(int64_t i, int64_t& io, int64_t& im) const {
+    const int64_t n = i / chw, rem = i - n * chw;
+    const int64_t ch = rem / hw, p = rem - ch * hw;
+    io = n * orig_sn + rem;
+    im = n * m_sn + ch * m_sc + p;
+  }
 };
 
 __device__ __forceinline__ float repaint_elem(float x, float e, float o, float m, float z, float sb, float sa, float clip,
                                               float sap, float dc, float sd, float sbp, bool add_std) {
-  const float p0 = pred_x0(x, e, sb, sa, clip);
-  float unknown = __fadd_rn(__fmul_rn(sap, p0), __fmul_rn(dc, e));
-  if (add_std) unknown = __fadd_rn(unknown, __fmul_rn(sd, z));
+  float unknown = ddim_combine(pred_x0(x, e, sb, sa, clip), e, sap, dc);
+  if (add_std) unknown = add_scaled(unknown, sd, z);
   // (the empty asm pins this product in a register of its own: hipcc otherwise pairs it with sbp*z into v_pk_mul_f32 and sums
   //  the pair with v_pk_add_f32 ... op_sel:[0,1], the form tests/test_isa_policy.py bans; same arithmetic, same rounding)
   float ko = __fmul_rn(sap, o);
   asm volatile("" : "+v"(ko));
-  const float known = __fadd_rn(ko, __fmul_rn(sbp, z));
-  return __fadd_rn(__fmul_rn(m, known), __fmul_rn(__fsub_rn(1.0f, m), unknown));
+  const float known = add_scaled(ko, sbp, z);
+  return axpby(m, known, __fsub_rn(1.0f, m), unknown);
 }
 
-template <int SRC>
-__device__ __forceinline__ void repaint_noise4(const float* nz, int64_t c, int64_t numel, bool vec, uint32_t seed_lo,
-                                               uint32_t seed_hi, uint32_t off_lo, uint32_t off_hi, float (&z)[4]) {
-  const int64_t e = c << 2;
-  if (SRC == 0) {
-    if (vec) {
-      const float4 v = *reinterpret_cast<const float4*>(nz + e);
-      z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
-    } else {
-      for (int k = 0; k < 4; ++k) z[k] = e + k < numel ? nz[e + k] : 0.f;
-    }
-  } else {
-    uint32_t r[4];
-    philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), off_lo, off_hi, seed_lo, seed_hi, r);
-    box_muller(r[0], r[1], z[0], z[1]);
-    box_muller(r[2], r[3], z[2], z[3]);
-  }
-}
-
-template <int SRC, bool VEC>
+template <int NOISE, bool VEC>
 __global__ __launch_bounds__(256) void repaint_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                                            const float* __restrict__ orig, const float* __restrict__ mask,
                                                            const float* __restrict__ nz, float* __restrict__ prev,
                                                            float* __restrict__ noise_out, repaint_geom g, float sb, float sa,
                                                            float clip, float sap, float dc, float sd, float sbp, int add_std,
-                                                           uint32_t seed_lo, uint32_t seed_hi, uint32_t off_lo,
-                                                           uint32_t off_hi) {
-  const int64_t blocks = (g.numel + 3) >> 2;
-  const int64_t stride = (int64_t)gridDim.x * 256;
+                                                           philox_words w) {
   const bool sdz = add_std != 0;
-  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < blocks; c += stride) {
-    float z[4];
-    repaint_noise4<SRC>(nz, c, g.numel, VEC, seed_lo, seed_hi, off_lo, off_hi, z);
-    const int64_t e = c << 2;
-    if (VEC) {
-      const int64_t n = e / g.chw, rem = e - n * g.chw;
-      const int64_t ch = rem / g.hw, p = rem - ch * g.hw;
-      const float4 xv = *reinterpret_cast<const float4*>(x + e);
-      const float4 ev = *reinterpret_cast<const float4*>(eps + e);
-      const float4 ov = *reinterpret_cast<const float4*>(orig + n * g.orig_sn + rem);
-      const float4 mv = *reinterpret_cast<const float4*>(mask + n * g.m_sn + ch * g.m_sc + p);
-      float4 r;
-      r.x = repaint_elem(xv.x, ev.x, ov.x, mv.x, z[0], sb, sa, clip, sap, dc, sd, sbp, sdz);
-      r.y = repaint_elem(xv.y, ev.y, ov.y, mv.y, z[1], sb, sa, clip, sap, dc, sd, sbp, sdz);
-      r.z = repaint_elem(xv.z, ev.z, ov.z, mv.z, z[2], sb, sa, clip, sap, dc, sd, sbp, sdz);
-      r.w = repaint_elem(xv.w, ev.w, ov.w, mv.w, z[3], sb, sa, clip, sap, dc, sd, sbp, sdz);
-      *reinterpret_cast<float4*>(prev + e) = r;
-      if (noise_out) *reinterpret_cast<float4*>(noise_out + e) = make_float4(z[0], z[1], z[2], z[3]);
+  for_each_quad(g.numel, [&](int64_t q, int64_t e) {
+    const bool vec = quad_is_vec<VEC>(e, g.numel);
+    float xv[4], ev[4], ov[4], mv[4], z[4], r[4];
+    load4(x, e, g.numel, vec, xv);
+    load4(eps, e, g.numel, vec, ev);
+    noise4<NOISE>(nz, noise_out, q, g.numel, vec, w, z);
+    if (vec) {                                    // (a VEC launch has hw % 4 == 0: the quad lies in one (n, c) plane)
+      int64_t io, im;
+      g.locate(e, io, im);
+      load4(orig, io, io + 4, true, ov);
+      load4(mask, im, im + 4, true, mv);
     } else {
-      for (int k = 0; k < 4 && e + k < g.numel; ++k) {
-        const int64_t i = e + k;
-        const int64_t n = i / g.chw, rem = i - n * g.chw;
-        const int64_t ch = rem / g.hw, p = rem - ch * g.hw;
-        prev[i] = repaint_elem(x[i], eps[i], orig[n * g.orig_sn + rem], mask[n * g.m_sn + ch * g.m_sc + p], z[k], sb, sa,
-                               clip, sap, dc, sd, sbp, sdz);
-        if (noise_out) noise_out[i] = z[k];
+      for (int k = 0; k < 4; ++k) {
+        int64_t io = 0, im = 0;
+        const bool in = e + k < g.numel;
+        if (in) g.locate(e + k, io, im);
+        ov[k] = in ? orig[io] : 0.f;
+        mv[k] = in ? mask[im] : 0.f;
       }
     }
-  }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = repaint_elem(xv[k], ev[k], ov[k], mv[k], z[k], sb, sa, clip, sap, dc, sd, sbp, sdz);
+    store4(prev, e, g.numel, vec, r);
+  });
 }
 
 // RePaint's jump back in time (one forward-diffusion step): out = ck*x + cz*z, z as above
-template <int SRC, bool VEC>
+template <int NOISE, bool VEC>
 __global__ __launch_bounds__(256) void repaint_undo_kernel(const float* __restrict__ x, const float* __restrict__ nz,
                                                            float* __restrict__ out, int64_t numel, float ck, float cz,
-                                                           uint32_t seed_lo, uint32_t seed_hi, uint32_t off_lo,
-                                                           uint32_t off_hi) {
-  const int64_t blocks = (numel + 3) >> 2;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < blocks; c += stride) {
-    float z[4];
-    repaint_noise4<SRC>(nz, c, numel, VEC, seed_lo, seed_hi, off_lo, off_hi, z);
-    const int64_t e = c << 2;
-    if (VEC) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + e);
-      float4 r;
-      r.x = __fadd_rn(__fmul_rn(ck, xv.x), __fmul_rn(cz, z[0]));
-      r.y = __fadd_rn(__fmul_rn(ck, xv.y), __fmul_rn(cz, z[1]));
-      r.z = __fadd_rn(__fmul_rn(ck, xv.z), __fmul_rn(cz, z[2]));
-      r.w = __fadd_rn(__fmul_rn(ck, xv.w), __fmul_rn(cz, z[3]));
-      *reinterpret_cast<float4*>(out + e) = r;
-    } else {
-      for (int k = 0; k < 4 && e + k < numel; ++k) out[e + k] = __fadd_rn(__fmul_rn(ck, x[e + k]), __fmul_rn(cz, z[k]));
-    }
-  }
+                                                           philox_words w) {
+  for_each_quad(numel, [&](int64_t q, int64_t e) {
+    const bool vec = quad_is_vec<VEC>(e, numel);
+    float xv[4], z[4], r[4];
+    load4(x, e, numel, vec, xv);
+    noise4<NOISE>(nz, nullptr, q, numel, vec, w, z);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = axpby(ck, xv[k], cz, z[k]);
+    store4(out, e, numel, vec, r);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -285,9 +343,7 @@ __global__ __launch_bounds__(256) void repaint_undo_kernel(const float* __restri
 //   D10  = inv_r0*(m0 - m1)                               ORDER >= 2
 //   D11  = inv_r1*(m1 - m2);  dd = D10 - D11;  D1 = D10 + q*dd;  D2 = p*dd        ORDER == 3 (D1 = D10 at order 2)
 //   prev = kx*x + c0*m0  [+ c1*D1]  [+ c2*D2]  [+ cn*z]   summed left to right
-// The host passes signed coefficients.  z as in repaint_step_kernel (NOISE 1: read from `nz`, 2: this lane's Philox block;
-// 0: no noise term).  VEC: every pointer is 16-byte aligned, so a lane's 4 elements are one dwordx4 access per stream; the last
-// numel % 4 elements take the per-element path, as everything does without VEC.
+// The host passes signed coefficients.
 struct dpm_coef {
   float sigma_s, alpha_s, inv_r0, inv_r1, q, p, kx, c0, c1, c2, cn;
 };
@@ -295,22 +351,22 @@ struct dpm_coef {
 template <int ORDER, bool NOISE>
 __device__ __forceinline__ void dpm_elem(float x, float e, float m1, float m2, float z, const dpm_coef& k, float& prev,
                                          float& m0o) {
-  const float m0 = __fdiv_rn(__fsub_rn(x, __fmul_rn(k.sigma_s, e)), k.alpha_s);
-  float r = __fadd_rn(__fmul_rn(k.kx, x), __fmul_rn(k.c0, m0));
+  const float m0 = pred_x0(x, e, k.sigma_s, k.alpha_s, 0.f);
+  float r = axpby(k.kx, x, k.c0, m0);
   if (ORDER >= 2) {
     const float d10 = __fmul_rn(k.inv_r0, __fsub_rn(m0, m1));
     float d1 = d10;
     if (ORDER == 3) {
       const float d11 = __fmul_rn(k.inv_r1, __fsub_rn(m1, m2));
       const float dd = __fsub_rn(d10, d11);
-      d1 = __fadd_rn(d10, __fmul_rn(k.q, dd));
-      r = __fadd_rn(r, __fmul_rn(k.c1, d1));
-      r = __fadd_rn(r, __fmul_rn(k.c2, __fmul_rn(k.p, dd)));
+      d1 = add_scaled(d10, k.q, dd);
+      r = add_scaled(r, k.c1, d1);
+      r = add_scaled(r, k.c2, __fmul_rn(k.p, dd));
     } else {
-      r = __fadd_rn(r, __fmul_rn(k.c1, d1));
+      r = add_scaled(r, k.c1, d1);
     }
   }
-  if (NOISE) r = __fadd_rn(r, __fmul_rn(k.cn, z));
+  if (NOISE) r = add_scaled(r, k.cn, z);
   prev = r;
   m0o = m0;
 }
@@ -320,40 +376,20 @@ __global__ __launch_bounds__(256) void dpmsolver_step_kernel(const float* __rest
                                                              const float* __restrict__ m1, const float* __restrict__ m2,
                                                              const float* __restrict__ nz, float* __restrict__ prev,
                                                              float* __restrict__ m0_out, float* __restrict__ noise_out,
-                                                             int64_t numel, dpm_coef k, uint32_t seed_lo, uint32_t seed_hi,
-                                                             uint32_t off_lo, uint32_t off_hi) {
-  const int64_t blocks = (numel + 3) >> 2;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < blocks; c += stride) {
-    const int64_t e = c << 2;
-    const bool vec = VEC && e + 4 <= numel;
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (NOISE == 1) repaint_noise4<0>(nz, c, numel, vec, seed_lo, seed_hi, off_lo, off_hi, z);
-    if (NOISE == 2) repaint_noise4<1>(nz, c, numel, vec, seed_lo, seed_hi, off_lo, off_hi, z);
-    if (vec) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + e);
-      const float4 ev = *reinterpret_cast<const float4*>(eps + e);
-      float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av, r, m;
-      if (ORDER >= 2) av = *reinterpret_cast<const float4*>(m1 + e);
-      if (ORDER == 3) bv = *reinterpret_cast<const float4*>(m2 + e);
-      dpm_elem<ORDER, NOISE != 0>(xv.x, ev.x, av.x, bv.x, z[0], k, r.x, m.x);
-      dpm_elem<ORDER, NOISE != 0>(xv.y, ev.y, av.y, bv.y, z[1], k, r.y, m.y);
-      dpm_elem<ORDER, NOISE != 0>(xv.z, ev.z, av.z, bv.z, z[2], k, r.z, m.z);
-      dpm_elem<ORDER, NOISE != 0>(xv.w, ev.w, av.w, bv.w, z[3], k, r.w, m.w);
-      *reinterpret_cast<float4*>(prev + e) = r;
-      *reinterpret_cast<float4*>(m0_out + e) = m;
-      if (NOISE != 0 && noise_out) *reinterpret_cast<float4*>(noise_out + e) = make_float4(z[0], z[1], z[2], z[3]);
-    } else {
-      for (int j = 0; j < 4 && e + j < numel; ++j) {
-        const int64_t i = e + j;
-        float r, m;
-        dpm_elem<ORDER, NOISE != 0>(x[i], eps[i], ORDER >= 2 ? m1[i] : 0.f, ORDER == 3 ? m2[i] : 0.f, z[j], k, r, m);
-        prev[i] = r;
-        m0_out[i] = m;
-        if (NOISE != 0 && noise_out) noise_out[i] = z[j];
-      }
-    }
-  }
+                                                             int64_t numel, dpm_coef k, philox_words w) {
+  for_each_quad(numel, [&](int64_t q, int64_t e) {
+    const bool vec = quad_is_vec<VEC>(e, numel);
+    float xv[4], ev[4], av[4] = {0.f, 0.f, 0.f, 0.f}, bv[4] = {0.f, 0.f, 0.f, 0.f}, z[4], r[4], m[4];
+    load4(x, e, numel, vec, xv);
+    load4(eps, e, numel, vec, ev);
+    if (ORDER >= 2) load4(m1, e, numel, vec, av);
+    if (ORDER == 3) load4(m2, e, numel, vec, bv);
+    noise4<NOISE>(nz, noise_out, q, numel, vec, w, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dpm_elem<ORDER, NOISE != NOISE_NONE>(xv[j], ev[j], av[j], bv[j], z[j], k, r[j], m[j]);
+    store4(prev, e, numel, vec, r);
+    store4(m0_out, e, numel, vec, m);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -529,63 +565,41 @@ __global__ __launch_bounds__(256) void thr_scan_kernel(uint32_t* __restrict__ ws
   }
 }
 
-// p0 clamped to +-s and divided by s (IEEE division): the thresholded data prediction
-__device__ __forceinline__ float thr_x0(float x, float e, float sb, float sa, float s) {
-  return __fdiv_rn(clampf(pred_x0(x, e, sb, sa, 0.f), -s, s), s);
-}
-
-// The scales of the (up to) 4 consecutive elements from flat index e on: one division when they share a sample
-__device__ __forceinline__ void thr_scales4(const float* __restrict__ thr, int64_t e, int64_t per, float (&s)[4]) {
+// The scales of the quad from flat index e on: one division when its elements share a sample (then the quad is whole).
+// thr is read at index < numel / per only: an element past numel gets the scale 1.
+__device__ __forceinline__ void thr_scales4(const float* __restrict__ thr, int64_t e, int64_t numel, int64_t per, float (&s)[4]) {
   const int64_t n = e / per, rem = e - n * per;
   if (rem + 4 <= per) {
     s[0] = s[1] = s[2] = s[3] = thr[n];
-  } else {                                          // the quad crosses into the next sample(s): per % 4 != 0 only
-    for (int j = 0; j < 4; ++j) s[j] = thr[(e + j) / per];
+  } else {                                          // the quad crosses into the next sample(s), or past the end
+    for (int j = 0; j < 4; ++j) s[j] = e + j < numel ? thr[(e + j) / per] : 1.f;
   }
 }
 
-// MODE 0: DDPM (prev = c0*x0' + ct*x [+ sigma*z]), a = c0, b = ct, c = sigma;  1: DDIM (prev = sap*x0' + dc*e), a = sap, b = dc
-template <int MODE>
-__device__ __forceinline__ float thr_step_elem(float x, float e, float z, bool add_z, float s, float sb, float sa, float a, float b,
-                                               float c) {
-  const float p0 = thr_x0(x, e, sb, sa, s);
-  if (MODE == 1) return __fadd_rn(__fmul_rn(a, p0), __fmul_rn(b, e));
-  float r = __fadd_rn(__fmul_rn(a, p0), __fmul_rn(b, x));
-  if (add_z) r = __fadd_rn(r, __fmul_rn(c, z));
-  return r;
-}
-
-// One lane = 4 consecutive elements; VEC: every pointer is 16-byte aligned, so they move as one dwordx4 per stream; the last
-// numel % 4 elements take the per-element path, as everything does without VEC.  thr is read at index < numel / per only.
-template <int MODE, bool VEC>
+// The DDPM / DDIM step with the thresholded data prediction.
+// MODE 0: DDPM (ddpm_combine: a = c0, b = ct, c = sigma; NOISE_READ when the step has a noise term);  1: DDIM (ddim_combine:
+// a = sap, b = dc; NOISE_NONE)
+template <int MODE, int NOISE, bool VEC>
 __global__ __launch_bounds__(256) void thr_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                                        const float* __restrict__ nz, const float* __restrict__ thr,
                                                        float* __restrict__ prev, int64_t numel, int64_t per, float sb, float sa,
                                                        float a, float b, float c) {
-  const int64_t quads = (numel + 3) >> 2;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  const bool add_z = MODE == 0 && nz != nullptr;
-  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += stride) {
-    const int64_t e = q << 2;
-    if (VEC && e + 4 <= numel) {
-      float s[4];
-      thr_scales4(thr, e, per, s);
-      const float4 xv = *reinterpret_cast<const float4*>(x + e);
-      const float4 ev = *reinterpret_cast<const float4*>(eps + e);
-      float4 zv = make_float4(0.f, 0.f, 0.f, 0.f), r;
-      if (add_z) zv = *reinterpret_cast<const float4*>(nz + e);
-      r.x = thr_step_elem<MODE>(xv.x, ev.x, zv.x, add_z, s[0], sb, sa, a, b, c);
-      r.y = thr_step_elem<MODE>(xv.y, ev.y, zv.y, add_z, s[1], sb, sa, a, b, c);
-      r.z = thr_step_elem<MODE>(xv.z, ev.z, zv.z, add_z, s[2], sb, sa, a, b, c);
-      r.w = thr_step_elem<MODE>(xv.w, ev.w, zv.w, add_z, s[3], sb, sa, a, b, c);
-      *reinterpret_cast<float4*>(prev + e) = r;
-    } else {
-      for (int j = 0; j < 4 && e + j < numel; ++j) {
-        const int64_t i = e + j;
-        prev[i] = thr_step_elem<MODE>(x[i], eps[i], add_z ? nz[i] : 0.f, add_z, thr[i / per], sb, sa, a, b, c);
-      }
+  static_assert(NOISE != NOISE_PHILOX && (MODE == 0 || NOISE == NOISE_NONE), "the thresholded steps read their noise or have none");
+  for_each_quad(numel, [&](int64_t q, int64_t e) {
+    const bool vec = quad_is_vec<VEC>(e, numel);
+    float xv[4], ev[4], z[4], s[4], r[4];
+    load4(x, e, numel, vec, xv);
+    load4(eps, e, numel, vec, ev);
+    noise4<NOISE>(nz, nullptr, q, numel, vec, philox_words{}, z);
+    thr_scales4(thr, e, numel, per, s);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float p0 = thr_x0(xv[j], ev[j], sb, sa, s[j]);
+      r[j] = MODE == 1 ? ddim_combine(p0, ev[j], a, b) : ddpm_combine(p0, xv[j], a, b);
+      if (NOISE != NOISE_NONE) r[j] = ddpm_add_noise(r[j], c, z[j]);
     }
-  }
+    store4(prev, e, numel, vec, r);
+  });
 }
 
 // (x/2 + 0.5).clamp(0,1), NCHW -> NHWC.  grid = (ceil(hw/256), n)
@@ -609,10 +623,40 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restric
   }
 }
 
-static inline int stream_blocks(int64_t numel) {
-  int64_t b = cdiv64(numel, 256);
-  return (int)(b < 1 ? 1 : (b > 256 * 16 ? 256 * 16 : b));
+// ---------------------------------------------------------------------------------------------------------------
+// Host helpers of the entry points below.
+static inline int capped_blocks(int64_t lanes, int64_t cap) {
+  const int64_t b = cdiv64(lanes, 256);
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
+// grid of a grid-stride kernel whose lane owns one ELEMENT (ddpm_step, ddim_step) / one QUAD (philox and the quad kernels)
+static inline int elem_blocks(int64_t numel) { return capped_blocks(numel, 256 * 16); }
+static inline int quad_blocks(int64_t numel) { return capped_blocks(cdiv64(numel, 4), 256 * 32); }
+
+// NULL counts as aligned: a stream the launch does not touch does not keep it from being VEC
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+template <class... P>
+static inline bool all_aligned16(const P*... p) { return (aligned16(p) && ...); }
+
+// do [a, a + abytes) and [b, b + bbytes) share a byte?  (NULL overlaps nothing)
+static inline bool overlaps2(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
+  if (!a || !b) return false;
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y ? y - x < abytes : x - y < bbytes;
+}
+
+// A run-time value v in [0, N) as a template argument: calls f(std::integral_constant<int, v>{}).  The one way this file picks
+// a kernel instantiation: with_constant<2>(vec, [&](auto VEC) { launch kernel<decltype(VEC)::value != 0> ... }).
+template <int N, class F>
+static inline void with_constant(int v, F&& f) {
+  if constexpr (N > 1) {
+    if (v == N - 1) f(std::integral_constant<int, N - 1>{});
+    else with_constant<N - 1>(v, f);
+  } else {
+    f(std::integral_constant<int, 0>{});
+  }
+}
+#define DSG_CONST(c) (decltype(c)::value)
 
 }  // namespace dsg
 
@@ -631,7 +675,7 @@ DSG_API int dsg_ddpm_step(const float* sample, const float* eps, const float* no
                           float sigma, void* stream) {
   DSG_CHECK_ARG(sample && eps && prev, "dsg_ddpm_step: NULL pointer");
   DSG_CHECK_ARG(numel > 0, "dsg_ddpm_step: numel must be positive");
-  hipLaunchKernelGGL(dsg::ddpm_step_kernel, dim3(dsg::stream_blocks(numel)), dim3(256), 0,
+  hipLaunchKernelGGL(dsg::ddpm_step_kernel, dim3(dsg::elem_blocks(numel)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), sample, eps, noise, prev, numel, sqrt_beta_prod_t,
                      sqrt_alpha_prod_t, clip, coef_x0, coef_xt, sigma);
   DSG_LAUNCH_CHECK();
@@ -642,7 +686,7 @@ DSG_API int dsg_ddim_step(const float* sample, const float* eps, float* prev, in
                           float sqrt_alpha_prod_t, float clip, float sqrt_alpha_prev, float dir_coef, void* stream) {
   DSG_CHECK_ARG(sample && eps && prev, "dsg_ddim_step: NULL pointer");
   DSG_CHECK_ARG(numel > 0, "dsg_ddim_step: numel must be positive");
-  hipLaunchKernelGGL(dsg::ddim_step_kernel, dim3(dsg::stream_blocks(numel)), dim3(256), 0,
+  hipLaunchKernelGGL(dsg::ddim_step_kernel, dim3(dsg::elem_blocks(numel)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), sample, eps, prev, numel, sqrt_beta_prod_t, sqrt_alpha_prod_t,
                      clip, sqrt_alpha_prev, dir_coef);
   DSG_LAUNCH_CHECK();
@@ -655,26 +699,27 @@ DSG_API int dsg_postprocess(const float* x, void* out, int32_t n, int32_t c, int
   DSG_CHECK_ARG(mode >= 0 && mode <= 2, "dsg_postprocess: mode must be 0, 1 or 2");
   dim3 grid(dsg::cdiv(hw, 256), n);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (mode == 0) hipLaunchKernelGGL(dsg::postprocess_kernel<0>, grid, dim3(256), 0, st, x, out, c, hw);
-  else if (mode == 1) hipLaunchKernelGGL(dsg::postprocess_kernel<1>, grid, dim3(256), 0, st, x, out, c, hw);
-  else hipLaunchKernelGGL(dsg::postprocess_kernel<2>, grid, dim3(256), 0, st, x, out, c, hw);
+  dsg::with_constant<3>(mode, [&](auto MODE) {
+    hipLaunchKernelGGL(dsg::postprocess_kernel<DSG_CONST(MODE)>, grid, dim3(256), 0, st, x, out, c, hw);
+  });
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }
 
 namespace dsg {
-static inline int philox_blocks(int64_t numel) {
-  int64_t b = cdiv64(cdiv64(numel, 4), 256);
-  return (int)(b < 1 ? 1 : (b > 256 * 32 ? 256 * 32 : b));
+template <int MODE>
+static void philox_launch(const float* x0, const float* sa, const float* sb, float* noisy, void* out, int64_t numel, int64_t per,
+                          uint64_t seed, uint64_t offset, void* stream) {
+  const philox_words w = philox_words::of(seed, offset);
+  hipLaunchKernelGGL(philox_kernel<MODE>, dim3(quad_blocks(numel)), dim3(256), 0, static_cast<hipStream_t>(stream), x0, sa, sb,
+                     noisy, out, numel, per, w.seed_lo, w.seed_hi, w.off_lo, w.off_hi);
 }
 }  // namespace dsg
 
 DSG_API int dsg_philox_u32(uint32_t* out, int64_t numel, uint64_t seed, uint64_t offset, void* stream) {
   DSG_CHECK_ARG(out, "dsg_philox_u32: NULL pointer");
   DSG_CHECK_ARG(numel > 0, "dsg_philox_u32: numel must be positive");
-  hipLaunchKernelGGL(dsg::philox_kernel<0>, dim3(dsg::philox_blocks(numel)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (void*)out, numel,
-                     (int64_t)4, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32));
+  dsg::philox_launch<0>(nullptr, nullptr, nullptr, nullptr, out, numel, 4, seed, offset, stream);
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }
@@ -682,9 +727,7 @@ DSG_API int dsg_philox_u32(uint32_t* out, int64_t numel, uint64_t seed, uint64_t
 DSG_API int dsg_philox_normal(float* out, int64_t numel, uint64_t seed, uint64_t offset, void* stream) {
   DSG_CHECK_ARG(out, "dsg_philox_normal: NULL pointer");
   DSG_CHECK_ARG(numel > 0, "dsg_philox_normal: numel must be positive");
-  hipLaunchKernelGGL(dsg::philox_kernel<1>, dim3(dsg::philox_blocks(numel)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (void*)out, numel,
-                     (int64_t)4, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)offset, (uint32_t)(offset >> 32));
+  dsg::philox_launch<1>(nullptr, nullptr, nullptr, nullptr, out, numel, 4, seed, offset, stream);
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }
@@ -693,23 +736,12 @@ DSG_API int dsg_add_noise_philox(const float* x0, const float* sqrt_a, const flo
                                  int32_t n, int64_t per_sample, uint64_t seed, uint64_t offset, void* stream) {
   DSG_CHECK_ARG(x0 && sqrt_a && sqrt_1ma && noisy && noise, "dsg_add_noise_philox: NULL pointer");
   DSG_CHECK_ARG(n > 0 && per_sample > 0, "dsg_add_noise_philox: bad dims");
-  const int64_t numel = (int64_t)n * per_sample;
-  hipLaunchKernelGGL(dsg::philox_kernel<2>, dim3(dsg::philox_blocks(numel)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     x0, sqrt_a, sqrt_1ma, noisy, (void*)noise, numel, per_sample, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     (uint32_t)offset, (uint32_t)(offset >> 32));
+  dsg::philox_launch<2>(x0, sqrt_a, sqrt_1ma, noisy, noise, (int64_t)n * per_sample, per_sample, seed, offset, stream);
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }
 
 namespace dsg {
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-// do [a, a + abytes) and [b, b + bbytes) share a byte?  (NULL overlaps nothing)
-static inline bool overlaps2(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
-  if (!a || !b) return false;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y ? y - x < abytes : x - y < bbytes;
-}
-
 template <int PASS>
 static void thr_pass(const float* x, const float* e, uint32_t* ws, float* s, int32_t n, int64_t per, float sb, float sa,
                      uint32_t k_lo, uint32_t k_hi, float w, float max_value, bool vec, hipStream_t st) {
@@ -717,8 +749,9 @@ static void thr_pass(const float* x, const float* e, uint32_t* ws, float* s, int
   int64_t bps = cdiv64(per, 1024), cap = cdiv64(2048, n);
   if (bps > cap) bps = cap;
   const dim3 grid((unsigned)bps, (unsigned)n), block(256);
-  if (vec) hipLaunchKernelGGL((thr_hist_kernel<PASS, true>), grid, block, 0, st, x, e, ws, per, sb, sa);
-  else hipLaunchKernelGGL((thr_hist_kernel<PASS, false>), grid, block, 0, st, x, e, ws, per, sb, sa);
+  with_constant<2>(vec, [&](auto VEC) {
+    hipLaunchKernelGGL((thr_hist_kernel<PASS, DSG_CONST(VEC) != 0>), grid, block, 0, st, x, e, ws, per, sb, sa);
+  });
   hipLaunchKernelGGL((thr_scan_kernel<PASS>), dim3((unsigned)n), block, 0, st, ws, s, k_lo, k_hi, w, max_value);
 }
 }  // namespace dsg
@@ -759,7 +792,7 @@ DSG_API int dsg_dynthresh_scale(const float* sample, const float* eps, float* s,
   uint32_t* ws = static_cast<uint32_t*>(workspace);
   DSG_HIP(dsg::zero_words(ws, (size_t)n * dsg::THR_WORDS, st));
   // dwordx4 loads need every sample's first element on a 16-byte boundary
-  const bool vec = (per_sample & 3) == 0 && dsg::aligned16(sample) && dsg::aligned16(eps);
+  const bool vec = (per_sample & 3) == 0 && dsg::all_aligned16(sample, eps);
   const uint32_t lo = (uint32_t)k_lo, hi = (uint32_t)k_hi;
   dsg::thr_pass<1>(sample, eps, ws, s, n, per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, lo, hi, w, sample_max_value, vec, st);
   dsg::thr_pass<2>(sample, eps, ws, s, n, per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, lo, hi, w, sample_max_value, vec, st);
@@ -769,14 +802,26 @@ DSG_API int dsg_dynthresh_scale(const float* sample, const float* eps, float* s,
 }
 
 namespace dsg {
-static int thr_step_check(const char* who, const float* sample, const float* eps, const float* thr, const float* prev,
-                          int64_t numel, int64_t per) {
+// both thresholded steps: the checks, then thr_step_kernel<MODE, noise ? NOISE_READ : NOISE_NONE, every pointer aligned>
+template <int MODE>
+static int thr_step(const char* who, const float* sample, const float* eps, const float* noise, const float* thr, float* prev,
+                    int64_t numel, int64_t per, float sb, float sa, float a, float b, float c, void* stream) {
   if (!(sample && eps && thr && prev)) return fail(DSG_ERR_INVALID_ARG, "%s: NULL pointer", who);
   if (numel <= 0) return fail(DSG_ERR_INVALID_ARG, "%s: numel must be positive", who);
   if (per <= 0 || numel % per != 0)
     return fail(DSG_ERR_INVALID_ARG, "%s: per_sample=%lld does not divide numel=%lld", who, (long long)per, (long long)numel);
   if (overlaps2(prev, (uint64_t)numel * sizeof(float), thr, (uint64_t)(numel / per) * sizeof(float)))
     return fail(DSG_ERR_INVALID_ARG, "%s: prev overlaps thr", who);
+  const dim3 grid(quad_blocks(numel)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  with_constant<2>(noise != nullptr, [&](auto NZ) {
+    with_constant<2>(all_aligned16(sample, eps, noise, prev), [&](auto VEC) {
+      // (NOISE_READ exists for the DDPM form only: MODE 1 is always called without noise)
+      hipLaunchKernelGGL((thr_step_kernel<MODE, MODE == 0 ? DSG_CONST(NZ) : NOISE_NONE, DSG_CONST(VEC) != 0>), grid, block, 0, st,
+                         sample, eps, noise, thr, prev, numel, per, sb, sa, a, b, c);
+    });
+  });
+  DSG_LAUNCH_CHECK();
   return DSG_OK;
 }
 }  // namespace dsg
@@ -784,37 +829,15 @@ static int thr_step_check(const char* who, const float* sample, const float* eps
 DSG_API int dsg_ddpm_step_thr(const float* sample, const float* eps, const float* noise, const float* thr, float* prev,
                               int64_t numel, int64_t per_sample, float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float coef_x0,
                               float coef_xt, float sigma, void* stream) {
-  const int rc = dsg::thr_step_check("dsg_ddpm_step_thr", sample, eps, thr, prev, numel, per_sample);
-  if (rc != DSG_OK) return rc;
-  const bool vec = dsg::aligned16(sample) && dsg::aligned16(eps) && dsg::aligned16(noise) && dsg::aligned16(prev);
-  const dim3 grid(dsg::philox_blocks(numel)), block(256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec)
-    hipLaunchKernelGGL((dsg::thr_step_kernel<0, true>), grid, block, 0, st, sample, eps, noise, thr, prev, numel, per_sample,
-                       sqrt_beta_prod_t, sqrt_alpha_prod_t, coef_x0, coef_xt, sigma);
-  else
-    hipLaunchKernelGGL((dsg::thr_step_kernel<0, false>), grid, block, 0, st, sample, eps, noise, thr, prev, numel, per_sample,
-                       sqrt_beta_prod_t, sqrt_alpha_prod_t, coef_x0, coef_xt, sigma);
-  DSG_LAUNCH_CHECK();
-  return DSG_OK;
+  return dsg::thr_step<0>("dsg_ddpm_step_thr", sample, eps, noise, thr, prev, numel, per_sample, sqrt_beta_prod_t,
+                          sqrt_alpha_prod_t, coef_x0, coef_xt, sigma, stream);
 }
 
 DSG_API int dsg_ddim_step_thr(const float* sample, const float* eps, const float* thr, float* prev, int64_t numel,
                               int64_t per_sample, float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float sqrt_alpha_prev,
                               float dir_coef, void* stream) {
-  const int rc = dsg::thr_step_check("dsg_ddim_step_thr", sample, eps, thr, prev, numel, per_sample);
-  if (rc != DSG_OK) return rc;
-  const bool vec = dsg::aligned16(sample) && dsg::aligned16(eps) && dsg::aligned16(prev);
-  const dim3 grid(dsg::philox_blocks(numel)), block(256);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (vec)
-    hipLaunchKernelGGL((dsg::thr_step_kernel<1, true>), grid, block, 0, st, sample, eps, (const float*)nullptr, thr, prev, numel,
-                       per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, sqrt_alpha_prev, dir_coef, 0.f);
-  else
-    hipLaunchKernelGGL((dsg::thr_step_kernel<1, false>), grid, block, 0, st, sample, eps, (const float*)nullptr, thr, prev, numel,
-                       per_sample, sqrt_beta_prod_t, sqrt_alpha_prod_t, sqrt_alpha_prev, dir_coef, 0.f);
-  DSG_LAUNCH_CHECK();
-  return DSG_OK;
+  return dsg::thr_step<1>("dsg_ddim_step_thr", sample, eps, nullptr, thr, prev, numel, per_sample, sqrt_beta_prod_t,
+                          sqrt_alpha_prod_t, sqrt_alpha_prev, dir_coef, 0.f, stream);
 }
 
 DSG_API int dsg_repaint_step(const dsg_repaint_step_args* a, void* stream) {
@@ -835,22 +858,20 @@ DSG_API int dsg_repaint_step(const dsg_repaint_step_args* a, void* stream) {
   g.orig_sn = a->original_n == 1 ? 0 : g.chw;
   g.m_sc = a->mask_c == 1 ? 0 : g.hw;
   g.m_sn = a->mask_n == 1 ? 0 : g.hw * a->mask_c;
-  const bool vec = (g.hw & 3) == 0 && dsg::aligned16(a->sample) && dsg::aligned16(a->eps) && dsg::aligned16(a->original) &&
-                   dsg::aligned16(a->mask) && dsg::aligned16(a->prev) && dsg::aligned16(a->noise) &&
-                   dsg::aligned16(a->noise_out);
-  const dim3 grid(dsg::philox_blocks(g.numel)), block(256);
+  // hw % 4 == 0 on top of the alignment, for this kernel alone: `original` and `mask` are broadcast, so their dwordx4 load
+  // needs the whole quad inside ONE (n, c) plane (it also makes numel % 4 == 0: a VEC launch has no per-element tail)
+  const bool vec = (g.hw & 3) == 0 &&
+                   dsg::all_aligned16(a->sample, a->eps, a->original, a->mask, a->prev, a->noise, a->noise_out);
+  const dim3 grid(dsg::quad_blocks(g.numel)), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint32_t s0 = (uint32_t)a->seed, s1 = (uint32_t)(a->seed >> 32), o0 = (uint32_t)a->offset, o1 = (uint32_t)(a->offset >> 32);
-#define DSG_REPAINT_LAUNCH(SRC, VEC)                                                                                          \
-  hipLaunchKernelGGL((dsg::repaint_step_kernel<SRC, VEC>), grid, block, 0, st, a->sample, a->eps, a->original, a->mask,       \
-                     a->noise, a->prev, a->noise_out, g, a->sqrt_beta_prod_t, a->sqrt_alpha_prod_t, a->clip,                  \
-                     a->sqrt_alpha_prev, a->dir_coef, a->std, a->sqrt_beta_prev, a->add_std, s0, s1, o0, o1)
-  if (a->noise) {
-    if (vec) DSG_REPAINT_LAUNCH(0, true); else DSG_REPAINT_LAUNCH(0, false);
-  } else {
-    if (vec) DSG_REPAINT_LAUNCH(1, true); else DSG_REPAINT_LAUNCH(1, false);
-  }
-#undef DSG_REPAINT_LAUNCH
+  const dsg::philox_words w = dsg::philox_words::of(a->seed, a->offset);
+  dsg::with_constant<2>(a->noise == nullptr, [&](auto PHILOX) {
+    dsg::with_constant<2>(vec, [&](auto VEC) {
+      hipLaunchKernelGGL((dsg::repaint_step_kernel<dsg::NOISE_READ + DSG_CONST(PHILOX), DSG_CONST(VEC) != 0>), grid, block, 0, st,
+                         a->sample, a->eps, a->original, a->mask, a->noise, a->prev, a->noise_out, g, a->sqrt_beta_prod_t,
+                         a->sqrt_alpha_prod_t, a->clip, a->sqrt_alpha_prev, a->dir_coef, a->std, a->sqrt_beta_prev, a->add_std, w);
+    });
+  });
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }
@@ -859,51 +880,18 @@ DSG_API int dsg_repaint_undo(const float* sample, const float* noise, float* out
                              uint64_t seed, uint64_t offset, void* stream) {
   DSG_CHECK_ARG(sample && out, "dsg_repaint_undo: NULL pointer");
   DSG_CHECK_ARG(numel > 0, "dsg_repaint_undo: numel must be positive");
-  const bool vec = (numel & 3) == 0 && dsg::aligned16(sample) && dsg::aligned16(out) && dsg::aligned16(noise);
-  const dim3 grid(dsg::philox_blocks(numel)), block(256);
+  const dim3 grid(dsg::quad_blocks(numel)), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const uint32_t s0 = (uint32_t)seed, s1 = (uint32_t)(seed >> 32), o0 = (uint32_t)offset, o1 = (uint32_t)(offset >> 32);
-#define DSG_UNDO_LAUNCH(SRC, VEC)                                                                                     \
-  hipLaunchKernelGGL((dsg::repaint_undo_kernel<SRC, VEC>), grid, block, 0, st, sample, noise, out, numel, ck, cz, s0, \
-                     s1, o0, o1)
-  if (noise) {
-    if (vec) DSG_UNDO_LAUNCH(0, true); else DSG_UNDO_LAUNCH(0, false);
-  } else {
-    if (vec) DSG_UNDO_LAUNCH(1, true); else DSG_UNDO_LAUNCH(1, false);
-  }
-#undef DSG_UNDO_LAUNCH
+  const dsg::philox_words w = dsg::philox_words::of(seed, offset);
+  dsg::with_constant<2>(noise == nullptr, [&](auto PHILOX) {
+    dsg::with_constant<2>(dsg::all_aligned16(sample, out, noise), [&](auto VEC) {
+      hipLaunchKernelGGL((dsg::repaint_undo_kernel<dsg::NOISE_READ + DSG_CONST(PHILOX), DSG_CONST(VEC) != 0>), grid, block, 0, st,
+                         sample, noise, out, numel, ck, cz, w);
+    });
+  });
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }
-
-namespace dsg {
-// do [a, a + bytes) and [b, b + bytes) share a byte?  (NULL overlaps nothing)
-static inline bool overlaps(const void* a, const void* b, uint64_t bytes) {
-  if (!a || !b) return false;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y ? y - x < bytes : x - y < bytes;
-}
-
-template <int ORDER, int NOISE>
-static void dpmsolver_launch(const dsg_dpmsolver_step_args* a, bool vec, const float* nz, hipStream_t st) {
-  const dpm_coef k = {a->sigma_s, a->alpha_s, a->inv_r0, a->inv_r1, a->q, a->p, a->kx, a->c0, a->c1, a->c2, a->cn};
-  const dim3 grid(philox_blocks(a->numel)), block(256);
-  const uint32_t s0 = (uint32_t)a->seed, s1 = (uint32_t)(a->seed >> 32), o0 = (uint32_t)a->offset, o1 = (uint32_t)(a->offset >> 32);
-  if (vec)
-    hipLaunchKernelGGL((dpmsolver_step_kernel<ORDER, NOISE, true>), grid, block, 0, st, a->sample, a->eps, a->m1, a->m2, nz,
-                       a->prev, a->m0_out, a->noise_out, a->numel, k, s0, s1, o0, o1);
-  else
-    hipLaunchKernelGGL((dpmsolver_step_kernel<ORDER, NOISE, false>), grid, block, 0, st, a->sample, a->eps, a->m1, a->m2, nz,
-                       a->prev, a->m0_out, a->noise_out, a->numel, k, s0, s1, o0, o1);
-}
-
-template <int ORDER>
-static void dpmsolver_launch_order(const dsg_dpmsolver_step_args* a, bool vec, hipStream_t st) {
-  if (!a->add_noise) dpmsolver_launch<ORDER, 0>(a, vec, nullptr, st);
-  else if (a->noise) dpmsolver_launch<ORDER, 1>(a, vec, a->noise, st);
-  else dpmsolver_launch<ORDER, 2>(a, vec, nullptr, st);
-}
-}  // namespace dsg
 
 DSG_API int dsg_dpmsolver_step(const dsg_dpmsolver_step_args* a, void* stream) {
   DSG_CHECK_ARG(a, "dsg_dpmsolver_step: NULL args");
@@ -912,7 +900,8 @@ DSG_API int dsg_dpmsolver_step(const dsg_dpmsolver_step_args* a, void* stream) {
   DSG_CHECK_ARG(a->order >= 1 && a->order <= 3, "dsg_dpmsolver_step: order=%d is not 1, 2 or 3", a->order);
   DSG_CHECK_ARG(a->order < 2 || a->m1, "dsg_dpmsolver_step: order %d needs the history entry m1", a->order);
   DSG_CHECK_ARG(a->order < 3 || a->m2, "dsg_dpmsolver_step: order %d needs the history entry m2", a->order);
-  // what THIS call reads and writes (a history entry above the order, or a noise pointer without add_noise, is not touched)
+  // what THIS call reads and writes (a history entry above the order, or a noise pointer without add_noise, is not touched):
+  // the kernels get exactly the pointers checked here
   const float* m1 = a->order >= 2 ? a->m1 : nullptr;
   const float* m2 = a->order >= 3 ? a->m2 : nullptr;
   const float* nz = a->add_noise ? a->noise : nullptr;
@@ -922,19 +911,25 @@ DSG_API int dsg_dpmsolver_step(const dsg_dpmsolver_step_args* a, void* stream) {
   const void* outs[3] = {a->prev, a->m0_out, nout};
   for (int o = 0; o < 3; ++o) {
     for (int i = 0; i < 5; ++i)
-      DSG_CHECK_ARG(!dsg::overlaps(outs[o], ins[i], bytes), "dsg_dpmsolver_step: an output overlaps an input (output %d, input %d)",
-                    o, i);
+      DSG_CHECK_ARG(!dsg::overlaps2(outs[o], bytes, ins[i], bytes),
+                    "dsg_dpmsolver_step: an output overlaps an input (output %d, input %d)", o, i);
     for (int p = o + 1; p < 3; ++p)
-      DSG_CHECK_ARG(!dsg::overlaps(outs[o], outs[p], bytes), "dsg_dpmsolver_step: two outputs overlap (%d, %d)", o, p);
+      DSG_CHECK_ARG(!dsg::overlaps2(outs[o], bytes, outs[p], bytes), "dsg_dpmsolver_step: two outputs overlap (%d, %d)", o, p);
   }
-  const bool vec = dsg::aligned16(a->sample) && dsg::aligned16(a->eps) && dsg::aligned16(m1) && dsg::aligned16(m2) &&
-                   dsg::aligned16(nz) && dsg::aligned16(a->prev) && dsg::aligned16(a->m0_out) && dsg::aligned16(nout);
+  const bool vec = dsg::all_aligned16(a->sample, a->eps, m1, m2, nz, a->prev, a->m0_out, nout);
+  const int noise = !a->add_noise ? dsg::NOISE_NONE : (nz ? dsg::NOISE_READ : dsg::NOISE_PHILOX);
+  const dsg::dpm_coef k = {a->sigma_s, a->alpha_s, a->inv_r0, a->inv_r1, a->q, a->p, a->kx, a->c0, a->c1, a->c2, a->cn};
+  const dsg::philox_words w = dsg::philox_words::of(a->seed, a->offset);
+  const dim3 grid(dsg::quad_blocks(a->numel)), block(256);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  dsg_dpmsolver_step_args b = *a;     // the kernels get exactly the pointers checked above
-  b.m1 = m1; b.m2 = m2; b.noise = nz; b.noise_out = nout;
-  if (a->order == 1) dsg::dpmsolver_launch_order<1>(&b, vec, st);
-  else if (a->order == 2) dsg::dpmsolver_launch_order<2>(&b, vec, st);
-  else dsg::dpmsolver_launch_order<3>(&b, vec, st);
+  dsg::with_constant<3>(a->order - 1, [&](auto ORDER1) {
+    dsg::with_constant<3>(noise, [&](auto NZ) {
+      dsg::with_constant<2>(vec, [&](auto VEC) {
+        hipLaunchKernelGGL((dsg::dpmsolver_step_kernel<DSG_CONST(ORDER1) + 1, DSG_CONST(NZ), DSG_CONST(VEC) != 0>), grid, block, 0,
+                           st, a->sample, a->eps, m1, m2, nz, a->prev, a->m0_out, nout, a->numel, k, w);
+      });
+    });
+  });
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }

@@ -12,12 +12,18 @@ Host side (this file): the beta / alpha-bar tables, the integer timestep tables 
 scalars, computed with the same fp32 operation order as the reference so they are bit-identical.
 Device side: the elementwise tensor math, in libdsg.so (dsg_add_noise / dsg_ddpm_step / dsg_ddim_step / dsg_repaint_step /
 dsg_repaint_undo / dsg_dpmsolver_step; with ``thresholding=True``: dsg_dynthresh_scale + dsg_ddpm_step_thr / dsg_ddim_step_thr).
+
+Layout: ``_SchedulerBase`` holds what all four classes share (config handling, the tables, ``add_noise``, config I/O, the
+memo helper); ``_Thresholding`` is the dynamic-thresholding mixin of DDPM and DDIM; ``_NoiseSource`` is the device-noise switch
+of RePaint and DPM-Solver.  Every ``step`` that takes a noise tensor resolves it through ``_resolve_noise`` -- one place that
+decides where the noise comes from, checks its shape and makes it contiguous fp32 on the sample's device.
 """
 from __future__ import annotations
 
 import json
 import os
 from types import SimpleNamespace
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -64,17 +70,47 @@ class HostNoise:
             self.consumed.synchronize()
 
 
-class DDPMScheduler:
-    config_name = "scheduler_config.json"
-    _class_name = "DDPMScheduler"
-    order = 1
+class _StepNoise(NamedTuple):
+    """What a step kernel is told about its noise: `ptr` to read it from (None: none, or made in the kernel from the Philox
+    tensor (`seed`, `offset`)), `tensor` to keep alive until the launch, `host` to tell when the kernel has read it."""
+    ptr: Optional[int] = None
+    tensor: Optional[torch.Tensor] = None
+    host: Optional[HostNoise] = None
+    seed: int = 0
+    offset: int = 0
 
-    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
-                     trained_betas=None, variance_type="fixed_small", clip_sample=True, prediction_type="epsilon",
-                     thresholding=False, dynamic_thresholding_ratio=0.995, clip_sample_range=1.0,
-                     sample_max_value=1.0, timestep_spacing="leading", steps_offset=0)
-    # config keys this engine runs at their default value only
-    _fixed_keys = ("beta_schedule", "trained_betas", "prediction_type", "timestep_spacing")
+
+def _resolve_noise(variance_noise, sample, generator, source=None):
+    """Where one step's noise comes from, in this order: the caller's ``variance_noise`` (a ``HostNoise``, read in place, or a
+    tensor); the next Philox tensor of `source` (a ``_NoiseSource`` in device mode), made inside the kernel; a draw from
+    `generator`, as diffusers makes it.  A tensor is checked against the sample's shape and handed over contiguous, fp32 and on
+    the sample's device: the kernels read `sample.numel()` floats from the pointer."""
+    shape = tuple(sample.shape)
+    if variance_noise is None:
+        if source is not None and source.noise_mode == "device":
+            return _StepNoise(seed=source.noise_seed, offset=source._next_offset())
+        variance_noise = _randn_like_reference(shape, generator, sample.device, sample.dtype)
+    if tuple(variance_noise.shape) != shape:
+        raise ValueError(f"variance_noise has shape {tuple(variance_noise.shape)}, the sample {shape}")
+    if isinstance(variance_noise, HostNoise):        # pinned host buffer: the kernel reads it in place
+        return _StepNoise(ptr=variance_noise.device_ptr, host=variance_noise)
+    z = variance_noise.to(sample.device, torch.float32).contiguous()
+    return _StepNoise(ptr=_lib.ptr(z), tensor=z)
+
+
+def _record_consumed(noise, device):
+    """Behind the launch that read `noise` (on `device`'s current stream): lets a ``HostNoise``'s owner reuse the buffer."""
+    if noise.host is not None:
+        noise.host.consumed = torch.cuda.Event()
+        noise.host.consumed.record(torch.cuda.current_stream(device))
+
+
+class _SchedulerBase:
+    """What the four schedulers share: config handling, the beta / alpha-bar tables, ``add_noise``, config I/O."""
+    config_name = "scheduler_config.json"
+    order = 1
+    _defaults = {}
+    _fixed_keys = ()        # config keys this engine runs at their default value only
 
     def __init__(self, **kwargs):
         cfg = dict(self._defaults)
@@ -87,7 +123,6 @@ class DDPMScheduler:
                 raise NotImplementedError(f"{self._class_name}: {key}={cfg[key]!r} is outside the DriveSceneGen "
                                           f"path (supported: {self._defaults[key]!r})")
         self._check_extra(cfg)
-        self._check_thresholding(cfg)
         self.config = FrozenConfig(**cfg)
         n = cfg["num_train_timesteps"]
         self.betas = torch.linspace(cfg["beta_start"], cfg["beta_end"], n, dtype=torch.float32)
@@ -100,26 +135,18 @@ class DDPMScheduler:
         self.timesteps = torch.from_numpy(np.arange(0, n)[::-1].copy())
         self._dev_tables = {}
         self._scalar_cache = {}
-        self._rank_cache = {}           # (per, q) -> (k_lo, k_hi, w) of the thresholding quantile
-        self._thr_buffers = {}          # (device, n) -> (workspace, workspace bytes, s [n])
 
     def _check_extra(self, cfg):
-        if cfg["variance_type"] != "fixed_small":
-            raise NotImplementedError("DDPMScheduler: only variance_type='fixed_small' (the reference default)")
+        """The class's own refusals, on the merged config."""
 
-    def _check_thresholding(self, cfg):
-        """Dynamic thresholding (diffusers' ``thresholding`` / ``dynamic_thresholding_ratio`` / ``sample_max_value``) where the
-        class runs it: DDPMScheduler and DDIMScheduler.  A class that keeps ``thresholding`` in ``_fixed_keys`` or has no such
-        key has refused already."""
-        if "thresholding" not in cfg or "thresholding" in self._fixed_keys:
-            return
-        if not isinstance(cfg["thresholding"], (bool, np.bool_)):
-            raise ValueError(f"{self._class_name}: thresholding={cfg['thresholding']!r} is not a bool")
-        q, m = cfg["dynamic_thresholding_ratio"], cfg["sample_max_value"]
-        if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 <= q <= 1.0:
-            raise ValueError(f"{self._class_name}: dynamic_thresholding_ratio={q!r} is outside [0, 1]")
-        if isinstance(m, bool) or not isinstance(m, (int, float, np.integer, np.floating)) or not 1.0 <= m < float("inf"):
-            raise ValueError(f"{self._class_name}: sample_max_value={m!r} is not a finite number >= 1")
+    @staticmethod
+    def _memo(cache, key, make):
+        """cache[key], made by `make()` on first use (the per-step scalars are a dozen 0-d tensor operations, ~50 us of host
+        time per denoising step otherwise)."""
+        hit = cache.get(key)
+        if hit is None:
+            hit = cache[key] = make()
+        return hit
 
     # training_pipeline.py:76 reads this attribute directly
     @property
@@ -131,20 +158,6 @@ class DDPMScheduler:
 
     def scale_model_input(self, sample, timestep=None):
         return sample
-
-    def set_timesteps(self, num_inference_steps: int, device=None):
-        n_train = self.config.num_train_timesteps
-        if num_inference_steps > n_train:
-            raise ValueError(f"num_inference_steps {num_inference_steps} > num_train_timesteps {n_train}")
-        self.num_inference_steps = num_inference_steps
-        ratio = n_train // num_inference_steps  # integer floor: 1000 // 750 == 1 (SURVEY headline finding 4)
-        ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
-        ts += self.config.steps_offset
-        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
-
-    def previous_timestep(self, t: int) -> int:
-        n = self.num_inference_steps if self.num_inference_steps else self.config.num_train_timesteps
-        return t - self.config.num_train_timesteps // n
 
     # ---- add_noise (training_pipeline.py:80; train.py:91 with an HWC image and timesteps=[1]) ----
     def _sqrt_tables(self, device):
@@ -199,45 +212,64 @@ class DDPMScheduler:
                                                        int(offset) & (2 ** 64 - 1), _lib.stream_ptr(x0.device)))
         return noisy, noise
 
-    # ---- reverse step -----------------------------------------------------------------------------
-    def step_scalars(self, t: int):
-        """fp32 scalars of DDPMScheduler.step for timestep t, in the reference's operation order (memoised per
-        (t, previous timestep): a dozen 0-d tensor operations, ~50 us of host time per denoising step otherwise)."""
-        key = (t, self.previous_timestep(t))
-        hit = self._scalar_cache.get(key)
-        if hit is None:
-            hit = self._scalar_cache[key] = self._step_scalars(t)
-        return hit
+    # ---- config I/O (App. A.5) ----------------------------------------------------------------------
+    def save_pretrained(self, save_directory):
+        os.makedirs(save_directory, exist_ok=True)
+        cfg = {"_class_name": self._class_name, "_diffusers_version": "0.20.0"}
+        cfg.update(self.config.to_dict())
+        with open(os.path.join(save_directory, self.config_name), "w") as f:
+            json.dump(cfg, f, indent=2, sort_keys=True)
+            f.write("\n")
 
-    def _step_scalars(self, t: int):
-        prev_t = self.previous_timestep(t)
-        a_t = self.alphas_cumprod[t]
-        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.one
-        b_t = 1 - a_t
-        b_prev = 1 - a_prev
-        cur_alpha = a_t / a_prev
-        cur_beta = 1 - cur_alpha
-        c0 = (a_prev ** 0.5 * cur_beta) / b_t
-        ct = cur_alpha ** 0.5 * b_prev / b_t
-        var = torch.clamp(b_prev / b_t * cur_beta, min=1e-20)
-        return dict(sqrt_beta_prod_t=float(b_t ** 0.5), sqrt_alpha_prod_t=float(a_t ** 0.5), coef_x0=float(c0),
-                    coef_xt=float(ct), sigma=float(var ** 0.5))
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, **_unused):
+        d = os.path.join(path, subfolder) if subfolder else path
+        with open(os.path.join(d, cls.config_name)) as f:
+            cfg = json.load(f)
+        cfg = {k: v for k, v in cfg.items() if k in cls._defaults}
+        return cls(**cfg)
 
-    # ---- dynamic thresholding ---------------------------------------------------------------------
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """A scheduler of THIS class from another's config: keys this class lacks are dropped (diffusers' swap idiom,
+        ``pipe.scheduler = Other.from_config(pipe.scheduler.config)``); `overrides` replace or add entries, as in diffusers."""
+        cfg = config.to_dict() if hasattr(config, "to_dict") else dict(config)
+        cfg = {k: v for k, v in cfg.items() if k in cls._defaults}
+        cfg.update(overrides)
+        return cls(**cfg)
+
+
+class _Thresholding:
+    """Dynamic thresholding (diffusers' ``thresholding`` / ``dynamic_thresholding_ratio`` / ``sample_max_value``) for the two
+    classes that run it, DDPMScheduler and DDIMScheduler."""
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self._rank_cache = {}           # (per, q) -> (k_lo, k_hi, w) of the thresholding quantile
+        self._thr_buffers = {}          # (device, n) -> (workspace, workspace bytes, s [n])
+
+    def _check_thresholding(self, cfg):
+        """Called from ``_check_extra`` of a class whose config has the three keys."""
+        if not isinstance(cfg["thresholding"], (bool, np.bool_)):
+            raise ValueError(f"{self._class_name}: thresholding={cfg['thresholding']!r} is not a bool")
+        q, m = cfg["dynamic_thresholding_ratio"], cfg["sample_max_value"]
+        if isinstance(q, bool) or not isinstance(q, (int, float, np.integer, np.floating)) or not 0.0 <= q <= 1.0:
+            raise ValueError(f"{self._class_name}: dynamic_thresholding_ratio={q!r} is outside [0, 1]")
+        if isinstance(m, bool) or not isinstance(m, (int, float, np.integer, np.floating)) or not 1.0 <= m < float("inf"):
+            raise ValueError(f"{self._class_name}: sample_max_value={m!r} is not a finite number >= 1")
+
     def threshold_ranks(self, per: int):
         """(k_lo, k_hi, w) of the ``dynamic_thresholding_ratio`` quantile of `per` values, as torch.quantile forms them: the
         rank is the fp32 product q * (per - 1).  Memoised per (per, q)."""
-        key = (int(per), float(self.config.dynamic_thresholding_ratio))
-        hit = self._rank_cache.get(key)
-        if hit is None:
-            rank = np.float32(key[1]) * np.float32(per - 1)
-            k_lo = int(np.floor(rank))
+        q = float(self.config.dynamic_thresholding_ratio)
+
+        def make():
+            rank = np.float32(q) * np.float32(per - 1)
             # (per - 1 above 2^24 may round UP on its way to fp32: no rank leaves the sample)
-            k_lo = min(k_lo, per - 1)
+            k_lo = min(int(np.floor(rank)), per - 1)
             k_hi = min(int(np.ceil(rank)), per - 1)
-            w = float(rank - np.float32(k_lo)) if k_hi > k_lo else 0.0
-            hit = self._rank_cache[key] = (k_lo, k_hi, w)
-        return hit
+            return k_lo, k_hi, float(rank - np.float32(k_lo)) if k_hi > k_lo else 0.0
+        return self._memo(self._rank_cache, (int(per), q), make)
 
     def _threshold_scale(self, x, e, s):
         """The per-sample scale of the thresholded data prediction, device fp32 [N] (``dsg_dynthresh_scale``; include/dsg.h).
@@ -268,23 +300,60 @@ class DDPMScheduler:
         if tuple(model_output.shape) != tuple(sample.shape):
             raise ValueError(f"{who}: model output {tuple(model_output.shape)} != sample {tuple(sample.shape)}")
 
+
+class DDPMScheduler(_Thresholding, _SchedulerBase):
+    _class_name = "DDPMScheduler"
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                     trained_betas=None, variance_type="fixed_small", clip_sample=True, prediction_type="epsilon",
+                     thresholding=False, dynamic_thresholding_ratio=0.995, clip_sample_range=1.0,
+                     sample_max_value=1.0, timestep_spacing="leading", steps_offset=0)
+    _fixed_keys = ("beta_schedule", "trained_betas", "prediction_type", "timestep_spacing")
+
+    def _check_extra(self, cfg):
+        if cfg["variance_type"] != "fixed_small":
+            raise NotImplementedError("DDPMScheduler: only variance_type='fixed_small' (the reference default)")
+        self._check_thresholding(cfg)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        n_train = self.config.num_train_timesteps
+        if num_inference_steps > n_train:
+            raise ValueError(f"num_inference_steps {num_inference_steps} > num_train_timesteps {n_train}")
+        self.num_inference_steps = num_inference_steps
+        ratio = n_train // num_inference_steps  # integer floor: 1000 // 750 == 1 (SURVEY headline finding 4)
+        ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
+        ts += self.config.steps_offset
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+
+    def previous_timestep(self, t: int) -> int:
+        n = self.num_inference_steps if self.num_inference_steps else self.config.num_train_timesteps
+        return t - self.config.num_train_timesteps // n
+
+    # ---- reverse step -----------------------------------------------------------------------------
+    def step_scalars(self, t: int):
+        """fp32 scalars of DDPMScheduler.step for timestep t, in the reference's operation order (memoised per
+        (t, previous timestep))."""
+        return self._memo(self._scalar_cache, (t, self.previous_timestep(t)), lambda: self._step_scalars(t))
+
+    def _step_scalars(self, t: int):
+        prev_t = self.previous_timestep(t)
+        a_t = self.alphas_cumprod[t]
+        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.one
+        b_t = 1 - a_t
+        b_prev = 1 - a_prev
+        cur_alpha = a_t / a_prev
+        cur_beta = 1 - cur_alpha
+        c0 = (a_prev ** 0.5 * cur_beta) / b_t
+        ct = cur_alpha ** 0.5 * b_prev / b_t
+        var = torch.clamp(b_prev / b_t * cur_beta, min=1e-20)
+        return dict(sqrt_beta_prod_t=float(b_t ** 0.5), sqrt_alpha_prod_t=float(a_t ** 0.5), coef_x0=float(c0),
+                    coef_xt=float(ct), sigma=float(var ** 0.5))
+
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, variance_noise=None):
         if not sample.is_cuda:
             raise RuntimeError("DDPMScheduler.step runs on the MI355X HIP engine only (got a CPU tensor)")
         t = int(timestep)
         s = self.step_scalars(t)
-        noise, host, nptr = None, None, None
-        if t > 0:
-            if isinstance(variance_noise, HostNoise):    # pinned host buffer: the kernel reads it in place
-                host = variance_noise
-                if tuple(host.shape) != tuple(sample.shape):
-                    raise ValueError(f"variance_noise has shape {tuple(host.shape)}, the sample {tuple(sample.shape)}")
-                nptr = host.device_ptr
-            else:
-                noise = variance_noise if variance_noise is not None else _randn_like_reference(
-                    model_output.shape, generator, model_output.device, model_output.dtype)
-                noise = noise.to(sample.device).contiguous()
-                nptr = _lib.ptr(noise)
+        nz = _resolve_noise(variance_noise, sample, generator) if t > 0 else _StepNoise()    # (t == 0 has no noise term)
         x, e = sample.contiguous(), model_output.contiguous()
         prev = torch.empty_like(x)
         clip = self.config.clip_sample_range if self.config.clip_sample else 0.0
@@ -292,45 +361,17 @@ class DDPMScheduler:
             if self.config.thresholding:        # (takes precedence over clip_sample, as in diffusers)
                 self._check_thresholded_inputs("DDPMScheduler.step", x, e)
                 scale, per = self._threshold_scale(x, e, s)
-                _lib.check(_lib.load().dsg_ddpm_step_thr(_lib.ptr(x), _lib.ptr(e), nptr, _lib.ptr(scale), _lib.ptr(prev),
+                _lib.check(_lib.load().dsg_ddpm_step_thr(_lib.ptr(x), _lib.ptr(e), nz.ptr, _lib.ptr(scale), _lib.ptr(prev),
                                                         x.numel(), per, s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"],
                                                         s["coef_x0"], s["coef_xt"], s["sigma"], _lib.stream_ptr(x.device)))
             else:
-                _lib.check(_lib.load().dsg_ddpm_step(_lib.ptr(x), _lib.ptr(e), nptr, _lib.ptr(prev), x.numel(),
+                _lib.check(_lib.load().dsg_ddpm_step(_lib.ptr(x), _lib.ptr(e), nz.ptr, _lib.ptr(prev), x.numel(),
                                                     s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"], clip, s["coef_x0"],
                                                     s["coef_xt"], s["sigma"], _lib.stream_ptr(x.device)))
-            if host is not None:
-                host.consumed = torch.cuda.Event()
-                host.consumed.record(torch.cuda.current_stream(x.device))
+            _record_consumed(nz, x.device)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev)
-
-    # ---- config I/O (App. A.5) ----------------------------------------------------------------------
-    def save_pretrained(self, save_directory):
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = {"_class_name": self._class_name, "_diffusers_version": "0.20.0"}
-        cfg.update(self.config.to_dict())
-        with open(os.path.join(save_directory, self.config_name), "w") as f:
-            json.dump(cfg, f, indent=2, sort_keys=True)
-            f.write("\n")
-
-    @classmethod
-    def from_pretrained(cls, path, subfolder=None, **_unused):
-        d = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(d, cls.config_name)) as f:
-            cfg = json.load(f)
-        cfg = {k: v for k, v in cfg.items() if k in cls._defaults}
-        return cls(**cfg)
-
-    @classmethod
-    def from_config(cls, config, **overrides):
-        """A scheduler of THIS class from another's config: keys this class lacks are dropped (diffusers' swap idiom,
-        ``pipe.scheduler = Other.from_config(pipe.scheduler.config)``); `overrides` replace or add entries, as in diffusers."""
-        cfg = config.to_dict() if hasattr(config, "to_dict") else dict(config)
-        cfg = {k: v for k, v in cfg.items() if k in cls._defaults}
-        cfg.update(overrides)
-        return cls(**cfg)
 
 
 class DDIMScheduler(DDPMScheduler):
@@ -344,17 +385,15 @@ class DDIMScheduler(DDPMScheduler):
     def _check_extra(self, cfg):
         if cfg["rescale_betas_zero_snr"]:
             raise NotImplementedError("DDIMScheduler: rescale_betas_zero_snr is outside the DriveSceneGen path")
+        self._check_thresholding(cfg)
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
-        self.final_alpha_cumprod = torch.tensor(1.0) if self.config.set_alpha_to_one else self.alphas_cumprod[0]
+        # (a subclass whose config has no such key -- RePaint -- ends at alpha-bar = 1, as diffusers' does)
+        self.final_alpha_cumprod = torch.tensor(1.0) if self.config.get("set_alpha_to_one", True) else self.alphas_cumprod[0]
 
     def step_scalars(self, t: int, eta: float = 0.0):
-        key = (t, self.previous_timestep(t), float(eta))
-        hit = self._scalar_cache.get(key)
-        if hit is None:
-            hit = self._scalar_cache[key] = self._step_scalars(t, eta)
-        return hit
+        return self._memo(self._scalar_cache, (t, self.previous_timestep(t), float(eta)), lambda: self._step_scalars(t, eta))
 
     def _step_scalars(self, t: int, eta: float = 0.0):
         prev_t = self.previous_timestep(t)
@@ -400,9 +439,10 @@ class DDIMScheduler(DDPMScheduler):
 
 
 class _NoiseSource:
-    """Where a scheduler's per-step noise comes from (``RePaintScheduler``, ``DPMSolverMultistepScheduler``): the caller's
-    generator (the default), or the Philox tensors (seed, offset), (seed, offset + 1), ... of ``dsg_philox_normal``, generated
-    inside the step kernel -- the same distribution, not the same values."""
+    """Where a scheduler's per-step noise comes from when the caller hands none in (``RePaintScheduler``,
+    ``DPMSolverMultistepScheduler``; read by ``_resolve_noise``): the caller's generator (the default), or the Philox tensors
+    (seed, offset), (seed, offset + 1), ... of ``dsg_philox_normal``, generated inside the step kernel -- the same distribution,
+    not the same values."""
 
     noise_mode, noise_seed, noise_offset = "host", None, 0
 
@@ -467,11 +507,10 @@ class RePaintScheduler(DDIMScheduler, _NoiseSource):
         pass
 
     def __init__(self, **kwargs):
-        DDPMScheduler.__init__(self, **kwargs)
-        self.final_alpha_cumprod = torch.tensor(1.0)
+        super().__init__(**kwargs)
         self.eta = float(self.config.eta)       # (diffusers: the pipeline overwrites this attribute per call)
         self._undo_cache = {}
-        self.noise_mode, self.noise_seed, self.noise_offset = "host", None, 0
+        self.use_host_noise()
 
     # ---- timestep table ---------------------------------------------------------------------------------------
     def set_timesteps(self, num_inference_steps: int, jump_length: int = 10, jump_n_sample: int = 10, device=None):
@@ -504,17 +543,15 @@ class RePaintScheduler(DDIMScheduler, _NoiseSource):
     def undo_scalars(self, t: int):
         """[(ck, cz)] of ``undo_step(sample, t)``'s passes (host mode), and the closed form of all of them (device mode)."""
         ratio = self.config.num_train_timesteps // self.num_inference_steps
-        key = (t, ratio)
-        hit = self._undo_cache.get(key)
-        if hit is None:
+
+        def make():
             if t < 0 or t + ratio > self.config.num_train_timesteps:
                 raise ValueError(f"RePaintScheduler.undo_step: timestep {t} + {ratio} passes leaves the beta table")
             betas = [self.betas[t + i] for i in range(ratio)]
             passes = [(float((1 - b) ** 0.5), float(b ** 0.5)) for b in betas]
             keep = float(np.prod([1.0 - float(b) for b in betas], dtype=np.float64))
-            fused = (float(np.float32(np.sqrt(keep))), float(np.float32(np.sqrt(1.0 - keep))))
-            hit = self._undo_cache[key] = (passes, fused)
-        return hit
+            return passes, (float(np.float32(np.sqrt(keep))), float(np.float32(np.sqrt(1.0 - keep))))
+        return self._memo(self._undo_cache, (t, ratio), make)
 
     # ---- reverse step -----------------------------------------------------------------------------------------
     def step(self, model_output, timestep, sample, original_image, mask, generator=None, return_dict: bool = True,
@@ -538,36 +575,19 @@ class RePaintScheduler(DDIMScheduler, _NoiseSource):
         x, e = sample.contiguous(), model_output.contiguous()
         orig = original_image.to(x.device, torch.float32).contiguous()
         m = mask.to(x.device, torch.float32).contiguous()
-        noise, host, nptr, seed, offset = None, None, None, 0, 0
-        if isinstance(variance_noise, HostNoise):
-            host = variance_noise
-            if tuple(host.shape) != full:
-                raise ValueError(f"variance_noise has shape {tuple(host.shape)}, the sample {full}")
-            nptr = host.device_ptr
-        elif variance_noise is not None:
-            noise = variance_noise.to(x.device, torch.float32).contiguous()
-            if tuple(noise.shape) != full:
-                raise ValueError(f"variance_noise has shape {tuple(noise.shape)}, the sample {full}")
-            nptr = _lib.ptr(noise)
-        elif self.noise_mode == "device":
-            seed, offset = self.noise_seed, self._next_offset()
-        else:
-            noise = _randn_like_reference(model_output.shape, generator, model_output.device, model_output.dtype).contiguous()
-            nptr = _lib.ptr(noise)
+        nz = _resolve_noise(variance_noise, x, generator, self)
         prev = torch.empty_like(x)
         a = _lib.RepaintStepArgs(
-            sample=_lib.ptr(x), eps=_lib.ptr(e), original=_lib.ptr(orig), mask=_lib.ptr(m), noise=nptr, prev=_lib.ptr(prev),
+            sample=_lib.ptr(x), eps=_lib.ptr(e), original=_lib.ptr(orig), mask=_lib.ptr(m), noise=nz.ptr, prev=_lib.ptr(prev),
             noise_out=None, n=full[0], c=full[1], h=full[2], w=full[3], original_n=int(orig.shape[0]),
             mask_n=int(m.shape[0]), mask_c=int(m.shape[1]), add_std=int(t > 0 and self.eta > 0),
             sqrt_beta_prod_t=s["sqrt_beta_prod_t"], sqrt_alpha_prod_t=s["sqrt_alpha_prod_t"],
             clip=1.0 if self.config.clip_sample else 0.0, sqrt_alpha_prev=s["sqrt_alpha_prev"], dir_coef=s["dir_coef"],
-            std=s["std"], sqrt_beta_prev=s["sqrt_beta_prev"], seed=seed, offset=offset)
+            std=s["std"], sqrt_beta_prev=s["sqrt_beta_prev"], seed=nz.seed, offset=nz.offset)
         import ctypes
         with torch.cuda.device(x.device):
             _lib.check(_lib.load().dsg_repaint_step(ctypes.byref(a), _lib.stream_ptr(x.device)))
-            if host is not None:
-                host.consumed = torch.cuda.Event()
-                host.consumed.record(torch.cuda.current_stream(x.device))
+            _record_consumed(nz, x.device)
         if not return_dict:
             return (prev,)
         return SchedulerOutput(prev_sample=prev)
@@ -585,32 +605,19 @@ class RePaintScheduler(DDIMScheduler, _NoiseSource):
         x = sample.contiguous()
         lib, st = _lib.load(), _lib.stream_ptr(x.device)
         with torch.cuda.device(x.device):
-            if self.noise_mode == "device" and variance_noise is None:
+            # device mode with nothing handed in: the closed form is ONE pass, its noise the scheduler's next Philox tensor
+            one_pass = self.noise_mode == "device" and variance_noise is None
+            for i, (ck, cz) in enumerate([fused] if one_pass else passes):
+                z = None if variance_noise is None else variance_noise() if callable(variance_noise) else variance_noise[i]
+                nz = _resolve_noise(z, x, generator, self)
                 out = torch.empty_like(x)
-                _lib.check(lib.dsg_repaint_undo(_lib.ptr(x), None, _lib.ptr(out), x.numel(), fused[0], fused[1],
-                                                self.noise_seed, self._next_offset(), st))
-                return out
-            for i, (ck, cz) in enumerate(passes):
-                if variance_noise is None:
-                    z = _randn_like_reference(x.shape, generator, x.device, x.dtype)
-                else:
-                    z = variance_noise() if callable(variance_noise) else variance_noise[i]
-                host = z if isinstance(z, HostNoise) else None
-                if tuple(z.shape) != tuple(x.shape):
-                    raise ValueError(f"undo_step: noise has shape {tuple(z.shape)}, the sample {tuple(x.shape)}")
-                if host is None:
-                    z = z.to(x.device, torch.float32).contiguous()
-                out = torch.empty_like(x)
-                _lib.check(lib.dsg_repaint_undo(_lib.ptr(x), host.device_ptr if host else _lib.ptr(z), _lib.ptr(out),
-                                                x.numel(), ck, cz, 0, 0, st))
-                if host is not None:
-                    host.consumed = torch.cuda.Event()
-                    host.consumed.record(torch.cuda.current_stream(x.device))
+                _lib.check(lib.dsg_repaint_undo(_lib.ptr(x), nz.ptr, _lib.ptr(out), x.numel(), ck, cz, nz.seed, nz.offset, st))
+                _record_consumed(nz, x.device)
                 x = out
         return x
 
 
-class DPMSolverMultistepScheduler(DDPMScheduler, _NoiseSource):
+class DPMSolverMultistepScheduler(_SchedulerBase, _NoiseSource):
     """diffusers-0.20.0 ``DPMSolverMultistepScheduler`` (Lu et al., "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion
     Probabilistic Models", 2022) in its data-prediction forms: ``algorithm_type`` "dpmsolver++" (the multistep exponential
     integrator of the diffusion ODE, orders 1-3; order 1 is DDIM) and "sde-dpmsolver++" (orders 1-2, one noise tensor per
@@ -715,10 +722,7 @@ class DPMSolverMultistepScheduler(DDPMScheduler, _NoiseSource):
         at s1 and s2 (memoised: some twenty 0-d tensor operations otherwise)."""
         key = (s0, t, s1 if order >= 2 else None, s2 if order >= 3 else None, order, self.config.algorithm_type,
                self.config.solver_type)
-        hit = self._scalar_cache.get(key)
-        if hit is None:
-            hit = self._scalar_cache[key] = self._step_scalars(s0, t, s1, s2, order)
-        return hit
+        return self._memo(self._scalar_cache, key, lambda: self._step_scalars(s0, t, s1, s2, order))
 
     def _step_scalars(self, s0, t, s1, s2, order):
         lam, al, sg = self.lambda_t, self.alpha_t, self.sigma_t
@@ -788,43 +792,23 @@ class DPMSolverMultistepScheduler(DDPMScheduler, _NoiseSource):
         s2 = self._hist_t[1] if order >= 3 else None
         s = self.step_scalars(s0, t, s1, s2, order)
         x, e = sample.contiguous(), model_output.contiguous()
-        full = tuple(x.shape)
         ring = self._history(x)
         K = len(ring)
         m1 = ring[self._head] if order >= 2 else None
         m2 = ring[(self._head - 1) % K] if order >= 3 else None
         slot = (self._head + 1) % K if self._hist_t else self._head     # the entry that falls out of the history
-        noise, host, nptr, seed, offset = None, None, None, 0, 0
         sde = self.needs_step_noise
-        if sde:
-            if isinstance(variance_noise, HostNoise):
-                host = variance_noise
-                if tuple(host.shape) != full:
-                    raise ValueError(f"variance_noise has shape {tuple(host.shape)}, the sample {full}")
-                nptr = host.device_ptr
-            elif variance_noise is not None:
-                noise = variance_noise.to(x.device, torch.float32).contiguous()
-                if tuple(noise.shape) != full:
-                    raise ValueError(f"variance_noise has shape {tuple(noise.shape)}, the sample {full}")
-                nptr = _lib.ptr(noise)
-            elif self.noise_mode == "device":
-                seed, offset = self.noise_seed, self._next_offset()
-            else:
-                noise = _randn_like_reference(model_output.shape, generator, model_output.device,
-                                              model_output.dtype).contiguous()
-                nptr = _lib.ptr(noise)
+        nz = _resolve_noise(variance_noise, x, generator, self) if sde else _StepNoise()
         prev = torch.empty_like(x)
         a = _lib.DpmSolverStepArgs(
-            sample=_lib.ptr(x), eps=_lib.ptr(e), m1=_lib.ptr(m1), m2=_lib.ptr(m2), noise=nptr, prev=_lib.ptr(prev),
+            sample=_lib.ptr(x), eps=_lib.ptr(e), m1=_lib.ptr(m1), m2=_lib.ptr(m2), noise=nz.ptr, prev=_lib.ptr(prev),
             m0_out=_lib.ptr(ring[slot]), noise_out=None, numel=x.numel(), order=order, add_noise=int(sde),
             sigma_s=s["sigma_s"], alpha_s=s["alpha_s"], inv_r0=s["inv_r0"], inv_r1=s["inv_r1"], q=s["q"], p=s["p"],
-            kx=s["kx"], c0=s["c0"], c1=s["c1"], c2=s["c2"], cn=s["cn"], seed=seed, offset=offset)
+            kx=s["kx"], c0=s["c0"], c1=s["c1"], c2=s["c2"], cn=s["cn"], seed=nz.seed, offset=nz.offset)
         import ctypes
         with torch.cuda.device(x.device):
             _lib.check(_lib.load().dsg_dpmsolver_step(ctypes.byref(a), _lib.stream_ptr(x.device)))
-            if host is not None:
-                host.consumed = torch.cuda.Event()
-                host.consumed.record(torch.cuda.current_stream(x.device))
+            _record_consumed(nz, x.device)
         self._head = slot
         self._hist_t = ([s0] + self._hist_t)[:K]
         if self.lower_order_nums < self.config.solver_order:

@@ -213,6 +213,19 @@ def test_ddpm_step_bit_exact(steps):
         assert torch.equal(got, want), (steps, t, max_abs(got, want))
 
 
+def test_ddpm_step_checks_and_casts_a_device_variance_noise():
+    """A device ``variance_noise`` goes through the same host-side resolution as a ``HostNoise``: one of the wrong shape is
+    refused before any launch (the kernel would read past its end), one of another dtype is used as its fp32 copy."""
+    import drivescenegen_amd as d
+    s = d.DDPMScheduler()
+    x, e = _t(64, (1, 1, 2, 2)).to(DEV), _t(65, (1, 1, 2, 2)).to(DEV)
+    with pytest.raises(ValueError):
+        s.step(e, 500, x, variance_noise=_t(66, (1, 1, 2, 1)).to(DEV))
+    z16 = _t(67, (1, 1, 2, 2)).to(DEV).half()
+    got = s.step(e, 500, x, variance_noise=z16).prev_sample
+    assert torch.equal(got, s.step(e, 500, x, variance_noise=z16.float()).prev_sample)
+
+
 @pytest.mark.parametrize("steps", [10, 50, 100])
 def test_ddim_step_bit_exact(steps):
     import drivescenegen_amd as d
