@@ -491,14 +491,23 @@ __global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(WgradP p, int ks
 typedef _Float16 whalf8 __attribute__((ext_vector_type(8)));
 typedef float wf32x16 __attribute__((ext_vector_type(16)));
 
+__device__ __forceinline__ void wsplit2(float v0, float v1, unsigned& hi, unsigned& lo) {  // two values -> packed (hi, hi), (lo, lo)
+  const _Float16 a0 = (_Float16)v0, a1 = (_Float16)v1;
+  const _Float16 b0 = (_Float16)((v0 - (float)a0) * 2048.0f), b1 = (_Float16)((v1 - (float)a1) * 2048.0f);
+  hi = (unsigned)__builtin_bit_cast(unsigned short, a0) | ((unsigned)__builtin_bit_cast(unsigned short, a1) << 16);
+  lo = (unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
+}
+
 // A lives in a ring of 6 patch rows (4 in use by the current stage + the 2 being written for the next one): a
 // workgroup walks consecutive row pairs of one 32-column strip of one image, so every input row is converted once.
 constexpr int WH_SLOTS = 6;
 constexpr int WH_ASTR = WH_SLOTS * 32 + 8;          // halfs per (shift, piece, ci): 6 rows x 32 columns + pad
 constexpr int WH_A_HALFS = 3 * 2 * 32 * WH_ASTR;    // [shift 3][piece 2][ci 32]
 constexpr int WH_DSTR = 64 + 8;                     // halfs per (piece, co): 2 rows x 32 columns + pad
-constexpr int WH_D_HALFS = 2 * 64 * WH_DSTR;        // [piece 2][co 64], double-buffered
-constexpr int WH_LDS_BYTES = (WH_A_HALFS + 2 * WH_D_HALFS) * 2;
+constexpr int wh_d_halfs(int co) { return 2 * co * WH_DSTR; }  // [piece 2][co] of a workgroup with co channels, double-buffered
+constexpr int WW_CO = 128;                          // couts per workgroup of the wide kernel
+constexpr int WH_D_HALFS = wh_d_halfs(WG_CO), WW_D_HALFS = wh_d_halfs(WW_CO);
+constexpr int WH_LDS_BYTES = (WH_A_HALFS + 2 * WH_D_HALFS) * 2, WW_LDS_BYTES = (WH_A_HALFS + 2 * WW_D_HALFS) * 2;
 
 // Workgroup -> (pair = (ci block, co block), slab = run of pixels) for the 3x3 weight-gradient kernels, grid = (pairs, slabs).
 // Workgroups go to the 8 XCDs in turn by their linear id, each XCD with an L2 of its own.  With the pair index fast the
@@ -538,74 +547,98 @@ __device__ __forceinline__ void wgrad_xcd_ids(int& pair, int& slab, int nrs = 0,
 #endif
 }
 
+// The half of the two fp16x2-split 3x3 kernels that does not depend on how the waves share the taps and co tiles: which run
+// the workgroup owns and how the run's rows of x and dY get from memory into the LDS layouts above.  CO = output channels per
+// workgroup (64: conv_wgrad_h2_kernel, 128: conv_wgrad_h2w_kernel).  Every member is inlined into the kernel and every u / part
+// is a constant at its call site after unrolling, so the state below lives in registers.  The kernels keep what they differ in:
+// the wave -> (tap, co tile) units, the fragment reads, the MFMA order and which k-step carries which staging call.
 // grid = (ci blocks x co blocks, strips x row splits); p.tiles_y = stages (row pairs) per image, p.ci_blocks as usual,
 // p.ntiles = row splits per strip (reused field), strips = n * tiles_x
-__global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char wsm[];
-  _Float16* ab = reinterpret_cast<_Float16*>(wsm);
-  _Float16* dbase = ab + WH_A_HALFS;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5;
-  const int l31 = lane & 31;
-  const int cot = wave & 1;
-  const bool first = wave < 2;  // taps 0..4; the other pair 5..8
-
-  int pair_id, slab_id;
-  wgrad_xcd_ids(pair_id, slab_id, p.ntiles, p.tiles_x);
-  const int cib = pair_id % p.ci_blocks;
-  const int cob = pair_id / p.ci_blocks;
-  const int ci0 = cib * 32, co0 = cob * WG_CO;
-  const int plane = p.hin * p.win;
-  const int oplane = p.hout * p.wout;
-  const bool has_ss = p.ss != nullptr;
-  const bool do_silu = has_ss && p.silu;
-
-  // this workgroup's run: strip (image n, column tile tx), stages [s0, s1)
-  const int nrs = p.ntiles;
-  const int strip = slab_id / nrs, rs = slab_id - strip * nrs;
-  const int n = strip / p.tiles_x, tx = strip - n * p.tiles_x;
-  const int ox0 = tx * 32;
-  const int per = (p.tiles_y + nrs - 1) / nrs;
-  const int s0 = rs * per, s1 = min(p.tiles_y, s0 + per);
-
-  // buffer descriptors (range-checked: reads before / past the tensor return 0, nothing faults) -- the ci block sits
-  // entirely in one of the two concatenated sources (c0 % 32 == 0)
-  const bool in0 = ci0 < p.c0;
-  const float* srcb = in0 ? p.src0 + ((size_t)n * p.c0 + ci0) * plane : p.src1 + ((size_t)n * p.c1 + (ci0 - p.c0)) * plane;
-  const float* src_all = in0 ? p.src0 : p.src1;
-  const size_t src_bytes = (size_t)p.n * (in0 ? p.c0 : p.c1) * plane * 4;
-  const int src_off = (int)((srcb - src_all) * 4);
-  const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src_all), 0, (int)src_bytes, 0x00020000);
-  const float* dyb = p.dy + ((size_t)n * p.dy_ctotal + p.dy_coff + co0) * oplane;
-  const __amdgpu_buffer_rsrc_t d_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dyb), 0, WG_CO * oplane * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t s_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(has_ss ? p.ss + ((size_t)n * p.cin + ci0) * 2 : p.dy), 0, has_ss ? 32 * 8 : 0, 0x00020000);
-
-  // staging items.  A: (ci, row of the pair, 8-column octet) -- one per thread; dY: (co, octet of the 2x32 stage) x 2
-  const int a_oct = tid & 3, a_rr = (tid >> 2) & 1, a_ci = tid >> 3;
-  const int a_voff = src_off + (a_ci * plane + a_rr * p.win + ox0 + a_oct * 8 - 1) * 4;  // + (2k-1)*win*4 per row pair
-  const unsigned a_colmask = 0x3FFu & ~((ox0 == 0 && a_oct == 0) ? 1u : 0u) & ~((ox0 + 32 == p.wc && a_oct == 3) ? 0x200u : 0u);
-  float sca = 1.f, sha = 0.f;
-  if (has_ss) {
-    const float2 s2 = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(s_rs, a_ci * 8, 0, 0));
-    sca = s2.x;
-    sha = s2.y;
-  }
-  int d_voff[2], d_lds[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int it = tid + 256 * u;
-    const int oct = it & 7, co = it >> 3;
-    d_voff[u] = (co * oplane + (oct >> 2) * p.wout + ox0 + (oct & 3) * 8) * 4;  // + 2s*wout*4 per stage
-    d_lds[u] = co * WH_DSTR + oct * 8;
-  }
-
+template <int CO>
+struct WgradH2Stage {
+  static constexpr int NU = CO / 32;              // dY items per thread
+  static constexpr int D_HALFS = wh_d_halfs(CO);  // one dY buffer
+  const WgradP& p;
+  _Float16* ab;     // LDS: the A ring [shift 3][piece 2][ci 32][slot 6][32]
+  _Float16* dbase;  // LDS: dY [buffer 2][piece 2][co CO][2 rows x 32 columns]
+  int tid, half, l31;
+  int cib, ci0, co0, slab_id;
+  int s0, s1;  // this workgroup's run: stages [s0, s1) of its strip
+  bool do_silu;
+  __amdgpu_buffer_rsrc_t a_rs, d_rs;
+  int a_oct, a_rr, a_ci, a_voff;
+  unsigned a_colmask;
+  float sca, sha;
+  int d_voff0, d_ustep, d_lds0;
   float xa[10];
-  float4 xd[2][2];
-  unsigned va = 0;
-  auto load_rows = [&](int k) {  // input rows 2k-1, 2k of the strip
+  float4 xd[NU][2];
+  unsigned va;
+  unsigned ph[5], pl[5];
+  float dsum[NU];  // this thread's (co, pixel octet) items of dY, summed over the run (cnt: 1 inside it, 0 past it)
+
+  __device__ __forceinline__ WgradH2Stage(const WgradP& p_, unsigned char* lds) : p(p_) {
+    ab = reinterpret_cast<_Float16*>(lds);
+    dbase = ab + WH_A_HALFS;
+    tid = threadIdx.x;
+    half = (tid & 63) >> 5;
+    l31 = tid & 31;
+    int pair_id;
+    wgrad_xcd_ids(pair_id, slab_id, p.ntiles, p.tiles_x);
+    cib = pair_id % p.ci_blocks;
+    const int cob = pair_id / p.ci_blocks;
+    ci0 = cib * 32;
+    co0 = cob * CO;
+    const int plane = p.hin * p.win;
+    const int oplane = p.hout * p.wout;
+    const bool has_ss = p.ss != nullptr;
+    do_silu = has_ss && p.silu;
+
+    // the run: strip (image n, column tile tx), stages [s0, s1)
+    const int nrs = p.ntiles;
+    const int strip = slab_id / nrs, rs = slab_id - strip * nrs;
+    const int n = strip / p.tiles_x, tx = strip - n * p.tiles_x;
+    const int ox0 = tx * 32;
+    const int per = (p.tiles_y + nrs - 1) / nrs;
+    s0 = rs * per;
+    s1 = min(p.tiles_y, s0 + per);
+
+    // buffer descriptors (range-checked: reads before / past the tensor return 0, nothing faults) -- the ci block sits
+    // entirely in one of the two concatenated sources (c0 % 32 == 0)
+    const bool in0 = ci0 < p.c0;
+    const float* srcb = in0 ? p.src0 + ((size_t)n * p.c0 + ci0) * plane : p.src1 + ((size_t)n * p.c1 + (ci0 - p.c0)) * plane;
+    const float* src_all = in0 ? p.src0 : p.src1;
+    const size_t src_bytes = (size_t)p.n * (in0 ? p.c0 : p.c1) * plane * 4;
+    const int src_off = (int)((srcb - src_all) * 4);
+    a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src_all), 0, (int)src_bytes, 0x00020000);
+    const float* dyb = p.dy + ((size_t)n * p.dy_ctotal + p.dy_coff + co0) * oplane;
+    d_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dyb), 0, CO * oplane * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t s_rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(has_ss ? p.ss + ((size_t)n * p.cin + ci0) * 2 : p.dy), 0, has_ss ? 32 * 8 : 0, 0x00020000);
+
+    // staging items.  A: (ci, row of the pair, 8-column octet) -- one per thread
+    a_oct = tid & 3;
+    a_rr = (tid >> 2) & 1;
+    a_ci = tid >> 3;
+    a_voff = src_off + (a_ci * plane + a_rr * p.win + ox0 + a_oct * 8 - 1) * 4;  // + (2k-1)*win*4 per row pair
+    a_colmask = 0x3FFu & ~((ox0 == 0 && a_oct == 0) ? 1u : 0u) & ~((ox0 + 32 == p.wc && a_oct == 3) ? 0x200u : 0u);
+    sca = 1.f;
+    sha = 0.f;
+    if (has_ss) {
+      const float2 s2 = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(s_rs, a_ci * 8, 0, 0));
+      sca = s2.x;
+      sha = s2.y;
+    }
+    // dY item u (of CO / 32) of this thread: co = (tid >> 3) + 32 u, octet tid & 7 of the 2 x 32 stage (the same for all its items)
+    const int d_oct = tid & 7;
+    d_voff0 = ((tid >> 3) * oplane + (d_oct >> 2) * p.wout + ox0 + (d_oct & 3) * 8) * 4;  // + u * d_ustep, + 2s*wout*4 per stage
+    d_ustep = 32 * oplane * 4;
+    d_lds0 = (tid >> 3) * WH_DSTR + d_oct * 8;  // + u * 32 * WH_DSTR
+    va = 0;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) dsum[u] = 0.f;
+  }
+
+  __device__ __forceinline__ void load_rows(int k) {  // input rows 2k-1, 2k of the strip
     const int off = a_voff + (2 * k - 1) * p.win * 4;
     // columns 0..7 of the octet as two aligned 16-byte loads, its left / right neighbours as single dwords (a
     // 16-byte access that starts before the tensor would be dropped as a whole by the range check)
@@ -616,25 +649,11 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
     xa[1] = q0.x; xa[2] = q0.y; xa[3] = q0.z; xa[4] = q0.w;
     xa[5] = q1.x; xa[6] = q1.y; xa[7] = q1.z; xa[8] = q1.w;
     va = ((unsigned)(2 * k - 1 + a_rr) < (unsigned)p.hc) ? a_colmask : 0u;
-  };
-  auto load_dy = [&](int s) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int off = d_voff[u] + 2 * s * p.wout * 4;
-      xd[u][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(d_rs, off, 0, 0));
-      xd[u][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(d_rs, off + 16, 0, 0));
-    }
-  };
-  auto split2 = [](float v0, float v1, unsigned& hi, unsigned& lo) {  // two values -> packed (hi, hi), (lo, lo)
-    const _Float16 a0 = (_Float16)v0, a1 = (_Float16)v1;
-    const _Float16 b0 = (_Float16)((v0 - (float)a0) * 2048.0f), b1 = (_Float16)((v1 - (float)a1) * 2048.0f);
-    hi = (unsigned)__builtin_bit_cast(unsigned short, a0) | ((unsigned)__builtin_bit_cast(unsigned short, a1) << 16);
-    lo = (unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
-  };
+  }
   // the values of load_rows(k) -> ring slots (2k) % 6, (2k + 1) % 6, three shifts; in two parts so that the work can
-  // be dealt over two k-steps of MFMAs (part 0: element pairs 0..2, part 1: pairs 3..4, the shifts and the writes)
-  unsigned ph[5], pl[5];
-  auto commit_rows = [&](int k, int part) {
+  // be dealt over two k-steps of MFMAs (part 0: element pairs 0..2, part 1: pairs 3..4, the shifts and the writes;
+  // any other part: all of it)
+  __device__ __forceinline__ void commit_rows(int k, int part) {
 #pragma unroll
     for (int j2 = (part == 1 ? 3 : 0); j2 < (part == 0 ? 3 : 5); ++j2) {
       float v[2];
@@ -646,7 +665,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
         x = do_silu ? sx : x;
         v[e] = ((va >> j) & 1u) ? x : 0.f;
       }
-      split2(v[0], v[1], ph[j2], pl[j2]);
+      wsplit2(v[0], v[1], ph[j2], pl[j2]);
     }
     if (part == 0) return;
     const int slot = (2 * k) % WH_SLOTS + a_rr;  // (2k % 6 is even, so + rr stays inside the ring)
@@ -667,23 +686,75 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
       *reinterpret_cast<uint4*>(dst + (s * 2 + 0) * 32 * WH_ASTR) = wh;
       *reinterpret_cast<uint4*>(dst + (s * 2 + 1) * 32 * WH_ASTR) = wl;
     }
-  };
-  float dsum[2] = {0.f, 0.f};  // this thread's two (co, pixel octet) items of dY, summed over the run (cnt: 1 inside it, 0 past it)
-  auto commit_dy = [&](int par, int u0, int u1, float cnt) {
-    _Float16* db = dbase + par * WH_D_HALFS;
+  }
+  __device__ __forceinline__ void load_dy(int s, int u0, int u1) {  // items [u0, u1) of output rows 2s, 2s+1
+#pragma unroll
+    for (int u = u0; u < u1; ++u) {
+      const int off = d_voff0 + u * d_ustep + 2 * s * p.wout * 4;
+      xd[u][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(d_rs, off, 0, 0));
+      xd[u][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(d_rs, off + 16, 0, 0));
+    }
+  }
+  // items [u0, u1) -> dY buffer par.  The main loops call this without a condition: past the run's last stage the values
+  // are never read and the loads were range-checked to zero (cnt = 0 keeps them out of the sums) -- a branch there
+  // would fence the scheduler
+  __device__ __forceinline__ void commit_dy(int par, int u0, int u1, float cnt) {
+    _Float16* db = dbase + par * D_HALFS + d_lds0;
 #pragma unroll
     for (int u = u0; u < u1; ++u) {
       dsum[u] += cnt * (((xd[u][0].x + xd[u][0].y) + (xd[u][0].z + xd[u][0].w)) +
                         ((xd[u][1].x + xd[u][1].y) + (xd[u][1].z + xd[u][1].w)));
       uint4 dh, dl;
-      split2(xd[u][0].x, xd[u][0].y, dh.x, dl.x);
-      split2(xd[u][0].z, xd[u][0].w, dh.y, dl.y);
-      split2(xd[u][1].x, xd[u][1].y, dh.z, dl.z);
-      split2(xd[u][1].z, xd[u][1].w, dh.w, dl.w);
-      *reinterpret_cast<uint4*>(db + d_lds[u]) = dh;
-      *reinterpret_cast<uint4*>(db + 64 * WH_DSTR + d_lds[u]) = dl;
+      wsplit2(xd[u][0].x, xd[u][0].y, dh.x, dl.x);
+      wsplit2(xd[u][0].z, xd[u][0].w, dh.y, dl.y);
+      wsplit2(xd[u][1].x, xd[u][1].y, dh.z, dl.z);
+      wsplit2(xd[u][1].z, xd[u][1].w, dh.w, dl.w);
+      *reinterpret_cast<uint4*>(db + u * 32 * WH_DSTR) = dh;
+      *reinterpret_cast<uint4*>(db + (CO + u * 32) * WH_DSTR) = dl;
     }
-  };
+  }
+  // row pairs s0 and s0+1 and dY(s0) into LDS; row pair s0+2 and dY(s0+1) into registers
+  __device__ __forceinline__ void prologue() {
+    if (s0 < s1) {
+      load_rows(s0);
+      load_dy(s0, 0, NU);
+      commit_rows(s0, 2);
+      load_rows(s0 + 1);
+      commit_dy(0, 0, NU, 1.f);
+      commit_rows(s0 + 1, 2);
+      load_rows(s0 + 2);               // (past the image: masked to zero)
+      if (s0 + 1 < s1) load_dy(s0 + 1, 0, NU);
+    }
+  }
+  // the by-product: one ci block per co block owns it; 8 neighbouring lanes share a co
+  __device__ __forceinline__ void store_dy_sums() {
+    if (p.dysum_ws != nullptr && cib == 0) {
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        float t = dsum[u];
+        t += __shfl_xor(t, 1, 64);
+        t += __shfl_xor(t, 2, 64);
+        t += __shfl_xor(t, 4, 64);
+        if ((tid & 7) == 0) p.dysum_ws[(size_t)slab_id * p.cout_pad + co0 + (tid >> 3) + 32 * u] = t;
+      }
+    }
+  }
+  // one accumulator tile D[ci][co = l31] of (tap, co tile of the workgroup) -> this run's slab [tap][ci][co]
+  // (register r of a lane holds ci = (r & 3) + 8 (r >> 2) + 4 half: the row offsets from the lane's first row are uniform)
+  __device__ __forceinline__ void store_tile(int tap, int co_tile, const wf32x16& hi, const wf32x16& lo) {
+    float* wsb = p.ws + (size_t)slab_id * 9 * p.cin_pad * p.cout_pad;
+    float* dst = wsb + ((size_t)tap * p.cin_pad + ci0 + 4 * half) * p.cout_pad + co0 + co_tile * 32 + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dst[(size_t)((r & 3) + 8 * (r >> 2)) * p.cout_pad] = hi[r] + lo[r] * (1.0f / 2048.0f);
+  }
+};
+
+__global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char wsm[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  WgradH2Stage<WG_CO> st(p, wsm);
+  const int cot = wave & 1;
+  const bool first = wave < 2;  // taps 0..4; the other pair 5..8
 
   wf32x16 acc_hi[5], acc_lo[5];
 #pragma unroll
@@ -694,27 +765,17 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
       acc_lo[t][r] = 0.f;
     }
 
-  // prologue: row pairs s0 and s0+1 and dY(s0) into LDS; row pair s0+2 and dY(s0+1) into registers
-  if (s0 < s1) {
-    load_rows(s0);
-    load_dy(s0);
-    commit_rows(s0, 2);
-    load_rows(s0 + 1);
-    commit_dy(0, 0, 2, 1.f);
-    commit_rows(s0 + 1, 2);
-    load_rows(s0 + 2);               // (past the image: masked to zero)
-    if (s0 + 1 < s1) load_dy(s0 + 1);
-  }
+  st.prologue();
   __syncthreads();
 
-  const _Float16* a_lane = ab + l31 * WH_ASTR + half * 8;
-  const _Float16* d_lane = dbase + (cot * 32 + l31) * WH_DSTR + half * 8;
+  const _Float16* a_lane = st.ab + st.l31 * WH_ASTR + st.half * 8;
+  const _Float16* d_lane = st.dbase + (cot * 32 + st.l31) * WH_DSTR + st.half * 8;
   // (one loop per tap half, not one loop with a branch inside: with the branch inside, the accumulators of the two
   // variants met in phi nodes and were copied between VGPRs and AGPRs every stage)
   auto run = [&](auto first_tag) {
-  for (int s = s0; s < s1; ++s) {
-    const int par = (s - s0) & 1;
-    const bool more = s + 1 < s1;
+  for (int s = st.s0; s < st.s1; ++s) {
+    const int par = (s - st.s0) & 1;
+    const bool more = s + 1 < st.s1;
     // ring slots of the 4 input rows of this stage: row j (0..3) = input row 2s - 1 + j -> slot (2s + j) % 6
     int slot_off[4];
 #pragma unroll
@@ -730,7 +791,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
       auto frags = [&](int kk, int fp) {
         const int orow = kk >> 1, colg = (kk & 1) * 16;
         fb[fp][0] = *reinterpret_cast<const whalf8*>(dl + orow * 32 + colg);
-        fb[fp][1] = *reinterpret_cast<const whalf8*>(dl + 64 * WH_DSTR + orow * 32 + colg);
+        fb[fp][1] = *reinterpret_cast<const whalf8*>(dl + WG_CO * WH_DSTR + orow * 32 + colg);
 #pragma unroll
         for (int tp = 0; tp < NTP; ++tp) {
           const int dy = (T0 + tp) / 3, dx = (T0 + tp) % 3;
@@ -746,17 +807,15 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
         if (kk < 3) frags(kk + 1, (kk + 1) & 1);
         // next stage's staging is dealt over the four k-steps and pinned between their MFMAs: patch rows (two
         // parts), then the two dY items; each fetch of the stage after it follows its commit at once
-        if (kk == 0) commit_rows(s + 2, 0);
+        if (kk == 0) st.commit_rows(s + 2, 0);
         if (kk == 1) {
-          commit_rows(s + 2, 1);
-          load_rows(s + 3);
+          st.commit_rows(s + 2, 1);
+          st.load_rows(s + 3);
         }
-        // (unconditional: past the run's last stage the values are never read and the loads are range-checked to
-        // zero -- a branch here would fence the scheduler)
-        if (kk == 2) commit_dy(par ^ 1, 0, 1, more ? 1.f : 0.f);
+        if (kk == 2) st.commit_dy(par ^ 1, 0, 1, more ? 1.f : 0.f);
         if (kk == 3) {
-          commit_dy(par ^ 1, 1, 2, more ? 1.f : 0.f);
-          load_dy(s + 2);
+          st.commit_dy(par ^ 1, 1, 2, more ? 1.f : 0.f);
+          st.load_dy(s + 2, 0, 2);
         }
         const int fp = kk & 1;
 #pragma unroll
@@ -779,30 +838,11 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
   if (first) run(std::true_type{});
   else run(std::false_type{});
 
-  if (p.dysum_ws != nullptr && cib == 0) {  // one ci block per co block owns the by-product; 8 neighbouring lanes share a co
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      float t = dsum[u];
-      t += __shfl_xor(t, 1, 64);
-      t += __shfl_xor(t, 2, 64);
-      t += __shfl_xor(t, 4, 64);
-      if ((tid & 7) == 0) p.dysum_ws[(size_t)slab_id * p.cout_pad + co0 + ((tid + 256 * u) >> 3)] = t;
-    }
-  }
-  // epilogue: D[ci][co = l31]; partials to this run's slab [tap][ci][co]
-  const int co = co0 + cot * 32 + l31;
-  float* wsb = p.ws + (size_t)slab_id * 9 * p.cin_pad * p.cout_pad;
+  st.store_dy_sums();
   const int t0 = first ? 0 : 5, ntp = first ? 5 : 4;
 #pragma unroll
-  for (int tp = 0; tp < 5; ++tp) {
-    if (tp < ntp) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ci = ci0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        wsb[((size_t)(t0 + tp) * p.cin_pad + ci) * p.cout_pad + co] = acc_hi[tp][r] + acc_lo[tp][r] * (1.0f / 2048.0f);
-      }
-    }
-  }
+  for (int tp = 0; tp < 5; ++tp)
+    if (tp < ntp) st.store_tile(t0 + tp, cot, acc_hi[tp], acc_lo[tp]);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -817,148 +857,16 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2_kernel(WgradP p) {
 // Per (ci, co, tap) the products are accumulated over a run's pixels in the 32 x 64 kernel's order: equal runs, equal bits.
 // LDS: the A ring as before (76.8 KB) + dY [buffer 2][piece 2][co 128][2 rows x 32 columns] (73.7 KB).
 // ---------------------------------------------------------------------------------------------------
-constexpr int WW_CO = 128;
-constexpr int WW_D_HALFS = 2 * WW_CO * WH_DSTR;
-constexpr int WW_LDS_BYTES = (WH_A_HALFS + 2 * WW_D_HALFS) * 2;
-
 __device__ __forceinline__ void mma_f16_vacc(const whalf8& a, const whalf8& b, wf32x16& c) {
   asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
 }
 
 __global__ __launch_bounds__(256, 1) void conv_wgrad_h2w_kernel(WgradP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char wsm[];
-  _Float16* ab = reinterpret_cast<_Float16*>(wsm);
-  _Float16* dbase = ab + WH_A_HALFS;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int half = lane >> 5;
-  const int l31 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  WgradH2Stage<WW_CO> st(p, wsm);
   const int cp = wave & 1;
   const bool first = wave < 2;  // tap group 0: taps 0..3 and the centre tap for co tile 2cp; group 1: 5..8, centre for 2cp + 1
-
-  int pair_id, slab_id;
-  wgrad_xcd_ids(pair_id, slab_id, p.ntiles, p.tiles_x);
-  const int cib = pair_id % p.ci_blocks;
-  const int cob = pair_id / p.ci_blocks;
-  const int ci0 = cib * 32, co0 = cob * WW_CO;
-  const int plane = p.hin * p.win;
-  const int oplane = p.hout * p.wout;
-  const bool has_ss = p.ss != nullptr;
-  const bool do_silu = has_ss && p.silu;
-
-  const int nrs = p.ntiles;
-  const int strip = slab_id / nrs, rs = slab_id - strip * nrs;
-  const int n = strip / p.tiles_x, tx = strip - n * p.tiles_x;
-  const int ox0 = tx * 32;
-  const int per = (p.tiles_y + nrs - 1) / nrs;
-  const int s0 = rs * per, s1 = min(p.tiles_y, s0 + per);
-
-  const bool in0 = ci0 < p.c0;
-  const float* srcb = in0 ? p.src0 + ((size_t)n * p.c0 + ci0) * plane : p.src1 + ((size_t)n * p.c1 + (ci0 - p.c0)) * plane;
-  const float* src_all = in0 ? p.src0 : p.src1;
-  const size_t src_bytes = (size_t)p.n * (in0 ? p.c0 : p.c1) * plane * 4;
-  const int src_off = (int)((srcb - src_all) * 4);
-  const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src_all), 0, (int)src_bytes, 0x00020000);
-  const float* dyb = p.dy + ((size_t)n * p.dy_ctotal + p.dy_coff + co0) * oplane;
-  const __amdgpu_buffer_rsrc_t d_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dyb), 0, WW_CO * oplane * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t s_rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(has_ss ? p.ss + ((size_t)n * p.cin + ci0) * 2 : p.dy), 0, has_ss ? 32 * 8 : 0, 0x00020000);
-
-  // staging items.  A: (ci, row of the pair, 8-column octet) -- one per thread; dY: (co, octet of the 2x32 stage) x 4
-  const int a_oct = tid & 3, a_rr = (tid >> 2) & 1, a_ci = tid >> 3;
-  const int a_voff = src_off + (a_ci * plane + a_rr * p.win + ox0 + a_oct * 8 - 1) * 4;
-  const unsigned a_colmask = 0x3FFu & ~((ox0 == 0 && a_oct == 0) ? 1u : 0u) & ~((ox0 + 32 == p.wc && a_oct == 3) ? 0x200u : 0u);
-  float sca = 1.f, sha = 0.f;
-  if (has_ss) {
-    const float2 s2 = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(s_rs, a_ci * 8, 0, 0));
-    sca = s2.x;
-    sha = s2.y;
-  }
-  // dY item u of this thread: co = (tid >> 3) + 32 u, octet tid & 7 (the same octet for its four items)
-  const int d_oct = tid & 7;
-  const int d_voff0 = ((tid >> 3) * oplane + (d_oct >> 2) * p.wout + ox0 + (d_oct & 3) * 8) * 4;  // + u * 32 * oplane * 4, + 2s*wout*4
-  const int d_lds0 = (tid >> 3) * WH_DSTR + d_oct * 8;                                           // + u * 32 * WH_DSTR
-  const int d_ustep = 32 * oplane * 4;
-
-  float xa[10];
-  float4 xd[4][2];
-  unsigned va = 0;
-  auto load_rows = [&](int k) {  // input rows 2k-1, 2k of the strip
-    const int off = a_voff + (2 * k - 1) * p.win * 4;
-    const float4 q0 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, off + 4, 0, 0));
-    const float4 q1 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, off + 20, 0, 0));
-    xa[0] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(a_rs, off, 0, 0));
-    xa[9] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(a_rs, off + 36, 0, 0));
-    xa[1] = q0.x; xa[2] = q0.y; xa[3] = q0.z; xa[4] = q0.w;
-    xa[5] = q1.x; xa[6] = q1.y; xa[7] = q1.z; xa[8] = q1.w;
-    va = ((unsigned)(2 * k - 1 + a_rr) < (unsigned)p.hc) ? a_colmask : 0u;
-  };
-  auto load_dy = [&](int s, int u0, int u1) {
-#pragma unroll
-    for (int u = u0; u < u1; ++u) {
-      const int off = d_voff0 + u * d_ustep + 2 * s * p.wout * 4;
-      xd[u][0] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(d_rs, off, 0, 0));
-      xd[u][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(d_rs, off + 16, 0, 0));
-    }
-  };
-  auto split2 = [](float v0, float v1, unsigned& hi, unsigned& lo) {
-    const _Float16 a0 = (_Float16)v0, a1 = (_Float16)v1;
-    const _Float16 b0 = (_Float16)((v0 - (float)a0) * 2048.0f), b1 = (_Float16)((v1 - (float)a1) * 2048.0f);
-    hi = (unsigned)__builtin_bit_cast(unsigned short, a0) | ((unsigned)__builtin_bit_cast(unsigned short, a1) << 16);
-    lo = (unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
-  };
-  unsigned ph[5], pl[5];
-  auto commit_rows = [&](int k, int part) {
-#pragma unroll
-    for (int j2 = (part == 1 ? 3 : 0); j2 < (part == 0 ? 3 : 5); ++j2) {
-      float v[2];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int j = 2 * j2 + e;
-        float x = xa[j] * sca + sha;
-        const float sx = silu_fast_b(x);
-        x = do_silu ? sx : x;
-        v[e] = ((va >> j) & 1u) ? x : 0.f;
-      }
-      split2(v[0], v[1], ph[j2], pl[j2]);
-    }
-    if (part == 0) return;
-    const int slot = (2 * k) % WH_SLOTS + a_rr;
-    _Float16* dst = ab + a_ci * WH_ASTR + slot * 32 + a_oct * 8;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      uint4 wh, wl;
-      if (s == 1) {
-        wh = make_uint4(__builtin_amdgcn_alignbit(ph[1], ph[0], 16), __builtin_amdgcn_alignbit(ph[2], ph[1], 16),
-                        __builtin_amdgcn_alignbit(ph[3], ph[2], 16), __builtin_amdgcn_alignbit(ph[4], ph[3], 16));
-        wl = make_uint4(__builtin_amdgcn_alignbit(pl[1], pl[0], 16), __builtin_amdgcn_alignbit(pl[2], pl[1], 16),
-                        __builtin_amdgcn_alignbit(pl[3], pl[2], 16), __builtin_amdgcn_alignbit(pl[4], pl[3], 16));
-      } else {
-        const int o = s >> 1;
-        wh = make_uint4(ph[o], ph[o + 1], ph[o + 2], ph[o + 3]);
-        wl = make_uint4(pl[o], pl[o + 1], pl[o + 2], pl[o + 3]);
-      }
-      *reinterpret_cast<uint4*>(dst + (s * 2 + 0) * 32 * WH_ASTR) = wh;
-      *reinterpret_cast<uint4*>(dst + (s * 2 + 1) * 32 * WH_ASTR) = wl;
-    }
-  };
-  float dsum[4] = {0.f, 0.f, 0.f, 0.f};
-  auto commit_dy = [&](int par, int u0, int u1, float cnt) {
-    _Float16* db = dbase + par * WW_D_HALFS + d_lds0;
-#pragma unroll
-    for (int u = u0; u < u1; ++u) {
-      dsum[u] += cnt * (((xd[u][0].x + xd[u][0].y) + (xd[u][0].z + xd[u][0].w)) +
-                        ((xd[u][1].x + xd[u][1].y) + (xd[u][1].z + xd[u][1].w)));
-      uint4 dh, dl;
-      split2(xd[u][0].x, xd[u][0].y, dh.x, dl.x);
-      split2(xd[u][0].z, xd[u][0].w, dh.y, dl.y);
-      split2(xd[u][1].x, xd[u][1].y, dh.z, dl.z);
-      split2(xd[u][1].z, xd[u][1].w, dh.w, dl.w);
-      *reinterpret_cast<uint4*>(db + u * 32 * WH_DSTR) = dh;
-      *reinterpret_cast<uint4*>(db + WW_CO * WH_DSTR + u * 32 * WH_DSTR) = dl;
-    }
-  };
 
   wf32x16 acc_hi[8], acc_lo[8], cen_hi, cen_lo;  // [tap of the group 4][co tile of the pair 2]; the centre unit (pinned)
 #pragma unroll
@@ -974,24 +882,15 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2w_kernel(WgradP p) {
       acc_lo[t][r] = 0.f;
     }
 
-  if (s0 < s1) {
-    load_rows(s0);
-    load_dy(s0, 0, 4);
-    commit_rows(s0, 2);
-    load_rows(s0 + 1);
-    commit_dy(0, 0, 4, 1.f);
-    commit_rows(s0 + 1, 2);
-    load_rows(s0 + 2);
-    if (s0 + 1 < s1) load_dy(s0 + 1, 0, 4);
-  }
+  st.prologue();
   __syncthreads();
 
-  const _Float16* a_lane = ab + l31 * WH_ASTR + half * 8;
-  const _Float16* d_lane = dbase + (cp * 64 + l31) * WH_DSTR + half * 8;
-  auto run = [&](auto first_tag) {
-  for (int s = s0; s < s1; ++s) {
-    const int par = (s - s0) & 1;
-    const bool more = s + 1 < s1;
+  const _Float16* a_lane = st.ab + st.l31 * WH_ASTR + st.half * 8;
+  const _Float16* d_lane = st.dbase + (cp * 64 + st.l31) * WH_DSTR + st.half * 8;
+  auto run = [&](auto first_tag) {  // (one loop per tap group, as in the 32 x 64 kernel)
+  for (int s = st.s0; s < st.s1; ++s) {
+    const int par = (s - st.s0) & 1;
+    const bool more = s + 1 < st.s1;
     int slot_off[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) slot_off[j] = ((2 * s + j) % WH_SLOTS) * 32;
@@ -1021,18 +920,18 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2w_kernel(WgradP p) {
       for (int kk = 0; kk < 4; ++kk) {
         __builtin_amdgcn_sched_barrier(0);
         if (kk < 3) frags(kk + 1, (kk + 1) & 1);
-        if (kk == 0) commit_rows(s + 2, 0);
+        if (kk == 0) st.commit_rows(s + 2, 0);
         if (kk == 1) {
-          commit_rows(s + 2, 1);
-          load_rows(s + 3);
+          st.commit_rows(s + 2, 1);
+          st.load_rows(s + 3);
         }
         if (kk == 2) {
-          commit_dy(par ^ 1, 0, 2, more ? 1.f : 0.f);
-          load_dy(s + 2, 0, 2);
+          st.commit_dy(par ^ 1, 0, 2, more ? 1.f : 0.f);
+          st.load_dy(s + 2, 0, 2);
         }
         if (kk == 3) {
-          commit_dy(par ^ 1, 2, 4, more ? 1.f : 0.f);
-          load_dy(s + 2, 2, 4);
+          st.commit_dy(par ^ 1, 2, 4, more ? 1.f : 0.f);
+          st.load_dy(s + 2, 2, 4);
         }
         const int fp = kk & 1;
         // the centre unit first (inline asm on a pinned tile: a whole k-step of other instructions follows before the
@@ -1063,38 +962,13 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_h2w_kernel(WgradP p) {
   if (first) run(std::true_type{});
   else run(std::false_type{});
 
-  if (p.dysum_ws != nullptr && cib == 0) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      float t = dsum[u];
-      t += __shfl_xor(t, 1, 64);
-      t += __shfl_xor(t, 2, 64);
-      t += __shfl_xor(t, 4, 64);
-      if ((tid & 7) == 0) p.dysum_ws[(size_t)slab_id * p.cout_pad + co0 + (tid >> 3) + 32 * u] = t;
-    }
-  }
-  // epilogue: D[ci][co = l31] per (tap, co tile); partials to this run's slab [tap][ci][co]
-  float* wsb = p.ws + (size_t)slab_id * 9 * p.cin_pad * p.cout_pad;
+  st.store_dy_sums();
   const int t0 = first ? 0 : 5;
 #pragma unroll
   for (int tp = 0; tp < 4; ++tp)
 #pragma unroll
-    for (int cj = 0; cj < 2; ++cj) {
-      const int co = co0 + (2 * cp + cj) * 32 + l31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int ci = ci0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        wsb[((size_t)(t0 + tp) * p.cin_pad + ci) * p.cout_pad + co] = acc_hi[tp * 2 + cj][r] + acc_lo[tp * 2 + cj][r] * (1.0f / 2048.0f);
-      }
-    }
-  {
-    const int co = co0 + (2 * cp + (first ? 0 : 1)) * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int ci = ci0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      wsb[((size_t)4 * p.cin_pad + ci) * p.cout_pad + co] = cen_hi[r] + cen_lo[r] * (1.0f / 2048.0f);
-    }
-  }
+    for (int cj = 0; cj < 2; ++cj) st.store_tile(t0 + tp, 2 * cp + cj, acc_hi[tp * 2 + cj], acc_lo[tp * 2 + cj]);
+  st.store_tile(4, 2 * cp + (first ? 0 : 1), cen_hi, cen_lo);
 }
 
 static bool wgrad_h2_wide(int cout) { return g_tune.wgrad_h2_wide && cout % WW_CO == 0; }
@@ -1134,8 +1008,6 @@ static int launch_wgrad(WgradP p, size_t ws_bytes, hipStream_t st) {
                     4.0 * ((double)p.n * p.cin * p.hin * p.win + (double)p.n * p.cout * p.hout * p.wout), st);
   hipLaunchKernelGGL(kern, dim3(pairs, nsplit), dim3(256), lds, st, p);
   DSG_LAUNCH_CHECK();
-  const int64_t slab = (int64_t)G::TAPS * p.cin_pad * p.cout_pad;
-  (void)slab;
   launch_wgrad_reduce(p.ws, nslab, G::TAPS, p.cin, p.cout, p.cin_pad, p.cout_pad, p.dw, st);
   prof_end(pi, st);
   DSG_LAUNCH_CHECK();
@@ -1182,8 +1054,6 @@ static int launch_wgrad_h2(WgradP p, size_t ws_bytes, hipStream_t st, float* dy_
   if (wide) hipLaunchKernelGGL(conv_wgrad_h2w_kernel, dim3(pairs, nslab), dim3(256), (size_t)WW_LDS_BYTES, st, p);
   else hipLaunchKernelGGL(conv_wgrad_h2_kernel, dim3(pairs, nslab), dim3(256), (size_t)WH_LDS_BYTES, st, p);
   DSG_LAUNCH_CHECK();
-  const int64_t slab = (int64_t)9 * p.cin_pad * p.cout_pad;
-  (void)slab;
   // (run index = (image, column tile, row split): an image's runs are consecutive)
   const DysumJob job = dysum_job(dy_sums ? p.dysum_ws : nullptr, p.tiles_x * rsplit, p.cout, p.n, dy_sums,
                                  dy_sums_stride ? dy_sums_stride : p.cout, dy_bias_grad);
@@ -1205,13 +1075,6 @@ static int launch_wgrad_h2(WgradP p, size_t ws_bytes, hipStream_t st, float* dy_
 // the flag is honoured all the same.
 // ---------------------------------------------------------------------------------------------------
 constexpr int WP_STR = 64 + 8;  // halfs per (piece, channel): 64 pixels + 16 bytes of padding
-
-__device__ __forceinline__ void wsplit2(float v0, float v1, unsigned& hi, unsigned& lo) {
-  const _Float16 a0 = (_Float16)v0, a1 = (_Float16)v1;
-  const _Float16 b0 = (_Float16)((v0 - (float)a0) * 2048.0f), b1 = (_Float16)((v1 - (float)a1) * 2048.0f);
-  hi = (unsigned)__builtin_bit_cast(unsigned short, a0) | ((unsigned)__builtin_bit_cast(unsigned short, a1) << 16);
-  lo = (unsigned)__builtin_bit_cast(unsigned short, b0) | ((unsigned)__builtin_bit_cast(unsigned short, b1) << 16);
-}
 
 // grid = (runs, ci blocks x co blocks); p.ci_blocks = cin / TM.  The run index is the fast one: consecutive workgroups
 // go to different XCDs, so each XCD's L2 holds ITS pixel runs of A and dY once and serves every (ci, co) tile pair of

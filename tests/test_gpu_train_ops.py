@@ -311,6 +311,61 @@ def test_wgrad_wide_workgroups_match_the_32x64_ones(case):
     assert torch.allclose(got[0][1], got[1][1], rtol=0, atol=2e-6 * float(dy.double().sum((2, 3)).abs().max()))
 
 
+_LONG_RUN_CASES = [(64, 64, 128, 14, 256, True, 8), (96, 32, 192, 8, 256, False, 2), (128, 0, 128, 8, 256, True, 6)]
+_long_run_refs = {}
+
+
+def _long_run_ref(case):
+    """Inputs and the fp64 reference of one case, computed once for its two legs and left unchanged."""
+    if case not in _long_run_refs:
+        c0, c1, cout, h, w, gn, batch = case
+        cin = c0 + c1
+        x0 = _t(81, (batch, c0, h, w))
+        x1 = _t(82, (batch, c1, h, w)) if c1 else None
+        gamma, beta = 1 + _t(85, (cin,), 0.1), _t(86, (cin,), 0.1)
+        xin = torch.cat([x0, x1], 1) if c1 else x0
+        a = F.silu(F.group_norm(xin.double(), 8, gamma.double(), beta.double(), 1e-5)) if gn else xin.double()
+        dy = _t(89, (batch, cout, h, w))
+        want = torch.nn.grad.conv2d_weight(a, (cout, cin, 3, 3), dy.double(), padding=1)
+        _long_run_refs[case] = (x0, x1, gamma, beta, dy, want.float(), dy.double().sum((2, 3)))
+    return _long_run_refs[case]
+
+
+@pytest.mark.parametrize("wide", [0, 1])
+@pytest.mark.parametrize("case", _LONG_RUN_CASES, ids=lambda c: "c%d+%d_o%d_%dx%d" % c[:5])
+def test_wgrad_split_long_uneven_and_empty_runs(case, wide):
+    """The steady state of the split 3x3 weight gradient's staging: runs long enough for the 6-row ring to wrap, runs that
+    start at a stage s0 with 2 * s0 % 6 != 0 and go on, and empty runs.  From wgrad_h2_runs (pairs = cin / 32 * cout / CO,
+    strips = batch * w / 32, stages = h / 2, rsplit = min(stages, cdiv(cdiv(512, pairs), strips)), runs of cdiv(stages,
+    rsplit) stages), with cin = 128 (4 ci blocks) and w = 256 (8 column strips: first, interior, last) in every case:
+      c64+64_o128_14x256, batch 8: strips 64, stages 7.  32 x 64: pairs 8, want 64, rsplit 1 -- one run [0, 7), the ring
+        wraps twice.  32 x 128: pairs 4, want 128, rsplit 2 -- runs [0, 4) [4, 7), the second starts at ring slot 2.
+      c96+32_o192_8x256, batch 2: 192 % 128 != 0, so wgrad_h2_wide = 1 runs the 32 x 64 kernel too.  strips 16, stages 4,
+        pairs 12, want 43, rsplit 3 -- runs [0, 2) [2, 4) [4, 4): the last is empty, an all-zero slab and zero dY sums.
+      c128+0_o128_8x256, batch 6: strips 48, stages 4.  32 x 128: pairs 4, want 128, rsplit 3 -- runs [0, 2) [2, 4) and an
+        empty one.  32 x 64: pairs 8, want 64, rsplit 2 -- runs [0, 2) [2, 4).
+    dW against fp64 conv2d_weight and the dY sums against the fp64 sums, at the tolerances of the random-shape test."""
+    c0, c1, cout, h, w, gn, batch = case
+    assert ops.wgrad_h2_supported(c0, c1, cout, h, w)
+    x0, x1, gamma, beta, dy, want, want_sums = _long_run_ref(case)
+    d = lambda t: None if t is None else t.to(DEV)
+    ss = ops.gn_scale_shift(d(x0), d(gamma), d(beta), 8, 1e-5, src1=d(x1)) if gn else None
+
+    def run(wide_switch):
+        with ops.tuning(wgrad_h2_wide=wide_switch):
+            dw = torch.zeros((cout, c0 + c1, 3, 3), device=DEV)
+            sums = torch.zeros((batch, cout), device=DEV)
+            ops.conv_wgrad(d(x0), d(dy), dw, src1=d(x1), ksize=3, gn_scale_shift=ss, silu=gn, dy_sums=sums, dy_sums_stride=cout)
+        return dw.cpu(), sums.cpu()
+
+    dw, sums = run(wide)
+    assert torch.allclose(sums.double(), want_sums, rtol=0, atol=2e-5 * float(want_sums.abs().max()))
+    _close(dw, want, rel=3e-5, ab=3e-5)
+    if wide and cout % 128 != 0:  # the switch has nothing to select: the same kernel, the same bits
+        dw0, sums0 = run(0)
+        assert torch.equal(dw, dw0) and torch.equal(sums, sums0)
+
+
 def test_wgrad_dy_sums_refused_where_not_a_by_product():
     """dy_sums is a by-product of the split 3x3 kernel (and of the 16-bit one); a call another kernel serves reports
     the request as unsupported instead of leaving the table unwritten."""
