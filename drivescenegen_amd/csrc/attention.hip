@@ -9,7 +9,7 @@
 //
 // Layout: qkv [N][3C][L] is the output of the fused q/k/v projection (a 1x1 conv over [N,C,L]);
 // channel = head*D + i, so a head's q/k/v are D rows of L contiguous floats.  out is [N][C][L].
-#include "dsg_h16.h"
+#include "att_mfma8.h"
 #include "tuning.h"
 
 namespace dsg {
@@ -139,34 +139,12 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 //   * V is the A operand with rows = the 8 head dims, a row of ONES (row 8 of the tile) accumulates the softmax
 //     denominator of exactly the P that was multiplied, the other rows are padding.
 // fp32-class accuracy as in conv_h2.hip: q, k, v and p are split x = hi + lo * 2^-11 (two fp16 parts), three MFMAs
-// per product, the 2^11-scaled cross terms in a second accumulator.
+// per product, the 2^11-scaled cross terms in a second accumulator (att_mfma8.h: operands, products, LDS images).
 // Workgroup = 8 waves x 32 queries of one (image, head); its K and V (fp16 pairs) sit in LDS, KT keys at a time.
 // ---------------------------------------------------------------------------------------------------
-typedef _Float16 att_half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 att_half8 __attribute__((ext_vector_type(8)));
-typedef short att_short4 __attribute__((ext_vector_type(4)));
-constexpr int ATM_KT = 512;                  // keys per LDS tile (35 KB of LDS: four workgroups per CU)
-constexpr int ATM_VSTR = ATM_KT + 4;         // V row stride in halfs (+8 bytes: rows fall into different banks)
-
-constexpr int ATM_NW = 8;                    // waves per workgroup: 256 queries share one conversion of K and V
 #ifndef DSG_ATM_MINW
 #define DSG_ATM_MINW 4
 #endif
-
-// fp32 -> the 16-bit operand type of PREC, carried in a _Float16-typed container (bits only)
-template <int PREC>
-__device__ __forceinline__ _Float16 att_cvt(float v) {
-  if constexpr (PREC == 1) return __builtin_bit_cast(_Float16, (__bf16)v);
-  else return (_Float16)v;
-}
-// 8-deep S^T = K^T Q step on the matrix cores
-template <int PREC>
-__device__ __forceinline__ f32x16 att_mma8(att_half4 a, att_half4 b, f32x16 c) {
-  if constexpr (PREC == 1)
-    return __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(__builtin_bit_cast(att_short4, a), __builtin_bit_cast(att_short4, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x8f16(a, b, c, 0, 0, 0);
-}
 
 // PREC 0: fp32-class accuracy (fp16 pairs, three MFMAs per product).  PREC 1 / 2 (the mixed-precision modes,
 // BASELINE.json configs[4] "MFMA bf16 attn"): q, k, v and the probabilities are rounded once to bf16 / fp16, ONE MFMA per
@@ -198,16 +176,11 @@ __global__ __launch_bounds__(64 * ATM_NW, DSG_ATM_MINW) void attention_mfma8_ker
   };
   __shared__ __attribute__((aligned(16))) _Float16 Kh[ATM_KT * 8], Kl[SPLIT ? ATM_KT * 8 : 8];          // [key][d]
   __shared__ __attribute__((aligned(16))) _Float16 Vh[9 * ATM_VSTR], Vl[SPLIT ? 9 * ATM_VSTR : 8];      // [d | ones][key]
+  const att_image<SPLIT, false> K(Kh, Kl);
+  const att_image<SPLIT, true> V(Vh, Vl);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-  // Workgroup id -> (query tile, head, image).  Consecutive ids go to the 8 XCDs in turn, each with its own L2: XCD k
-  // takes a CONTIGUOUS eighth of the (image, head, tile) list, so the query tiles of one head -- which all stream the
-  // same K and V -- run behind one L2 at about the same time, and K / V come from HBM once instead of once per XCD
-  // (the tile-major order spread a head's 8 tiles over the 8 XCDs: 4.1x the algorithmic traffic, profiles/r01*).
-  const int qtiles = (l + 32 * ATM_NW - 1) / (32 * ATM_NW);
-  int bid = blockIdx.x;
-  if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int qt = bid % qtiles, hn = bid / qtiles;
-  const int h = hn % heads, n = hn / heads;
+  const att_tile wg = att_tile_id(l, heads);   // (tile = 32 * ATM_NW queries)
+  const int h = wg.h, n = wg.n;
   const float* qp = qkv + ((size_t)n * 3 * c + h * 8) * l;
   const float* kp = qp + (size_t)c * l;
   const float* vp = kp + (size_t)c * l;
@@ -215,31 +188,21 @@ __global__ __launch_bounds__(64 * ATM_NW, DSG_ATM_MINW) void attention_mfma8_ker
   const char* qb = reinterpret_cast<const char*>(qkv) + ((size_t)n * 3 * c + h * 8) * l * ESZ;
   const char* kb = qb + (size_t)c * l * ESZ;
   const char* vb = kb + (size_t)c * l * ESZ;
-  const int q0 = (qt * ATM_NW + wave) * 32;  // this wave's 32 queries (l % 32 == 0; a wave past the end idles)
+  const int q0 = (wg.tile * ATM_NW + wave) * 32;  // this wave's 32 queries (l % 32 == 0; a wave past the end idles)
   const bool active = q0 < l;
   const int qi = min(q0 + l31, l - 1);
 
   // B operand of S^T = K^T Q: lane (query l31, half) holds d = 4 half .. 4 half + 3, pre-scaled into the log2 domain
-  att_half4 qh, ql;
+  att_h4<SPLIT> q;
   float qv8[8];
   if constexpr (BLK) load8(qb + (size_t)qi * 8 * ESZ, qv8);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float v = (BLK ? (half ? qv8[4 + i] : qv8[i]) : qp[(size_t)(4 * half + i) * l + qi]) * qscale;
-    if constexpr (SPLIT) {
-      const _Float16 a = (_Float16)v;
-      qh[i] = a;
-      ql[i] = (_Float16)((v - (float)a) * 2048.0f);
-    } else {
-      qh[i] = att_cvt<PREC>(v);
-    }
-  }
-  f32x16 o_hi, o_lo;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) o_hi[r] = o_lo[r] = 0.f;
+  for (int i = 0; i < 4; ++i)
+    q.set(i, att_split<PREC>((BLK ? (half ? qv8[4 + i] : qv8[i]) : qp[(size_t)(4 * half + i) * l + qi]) * qscale));
+  att_acc<SPLIT> o = {};
   float m = -1e30f;
   const int vrow = min(l31, 8);  // A operand of O = V P: row = head dim (8 = the ones row, beyond: its copy, ignored)
-  const _Float16 one16 = SPLIT ? (_Float16)1.0f : att_cvt<PREC>(1.0f), zero16 = __builtin_bit_cast(_Float16, (unsigned short)0);
+  const att_h1<SPLIT> one = att_split<PREC>(1.0f), zero = att_split<PREC>(0.0f);
 
   for (int j0 = 0; j0 < l; j0 += ATM_KT) {
     const int kt = min(ATM_KT, l - j0);
@@ -253,70 +216,33 @@ __global__ __launch_bounds__(64 * ATM_NW, DSG_ATM_MINW) void attention_mfma8_ker
           load8(kb + (size_t)(j0 + j) * 8 * ESZ, kv);
           load8(vb + (size_t)(j0 + j) * 8 * ESZ, vv);
         }
-        att_half8 k8, k8l;
+        att_h8<SPLIT> k8;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          if constexpr (SPLIT) {
-            const _Float16 ka = (_Float16)kv[i], va = (_Float16)vv[i];
-            k8[i] = ka;
-            k8l[i] = (_Float16)((kv[i] - (float)ka) * 2048.0f);
-            Vh[i * ATM_VSTR + j] = va;
-            Vl[i * ATM_VSTR + j] = (_Float16)((vv[i] - (float)va) * 2048.0f);
-          } else {
-            k8[i] = att_cvt<PREC>(kv[i]);
-            Vh[i * ATM_VSTR + j] = att_cvt<PREC>(vv[i]);
-          }
+          k8.set(i, att_split<PREC>(kv[i]));
+          V.store(j, i, att_split<PREC>(vv[i]));
         }
-        *reinterpret_cast<att_half8*>(&Kh[j * 8]) = k8;
-        if constexpr (SPLIT) *reinterpret_cast<att_half8*>(&Kl[j * 8]) = k8l;
+        K.store_row(j, k8);
       }
+    } else {
+      att_stage<PREC>(kp, 1.f, vp, 1.f, l, j0, kt, [&](int j, int i, att_h1<SPLIT> k, att_h1<SPLIT> v) {
+        K.store(j, i, k);
+        V.store(j, i, v);
+      });
     }
-    for (int e = tid; e < (BLK ? 0 : 8 * ATM_KT); e += 64 * ATM_NW) {
-      const int i = e / ATM_KT, j = e - i * ATM_KT;  // coalesced along the keys
-      float kv = 0.f, vv = 0.f;
-      if (j < kt) {
-        kv = kp[(size_t)i * l + j0 + j];
-        vv = vp[(size_t)i * l + j0 + j];
-      }
-      if constexpr (SPLIT) {
-        const _Float16 ka = (_Float16)kv, va = (_Float16)vv;
-        Kh[j * 8 + i] = ka;
-        Kl[j * 8 + i] = (_Float16)((kv - (float)ka) * 2048.0f);
-        Vh[i * ATM_VSTR + j] = va;
-        Vl[i * ATM_VSTR + j] = (_Float16)((vv - (float)va) * 2048.0f);
-      } else {
-        Kh[j * 8 + i] = att_cvt<PREC>(kv);
-        Vh[i * ATM_VSTR + j] = att_cvt<PREC>(vv);
-      }
-    }
-    for (int j = tid; j < ATM_KT; j += 64 * ATM_NW) {
-      Vh[8 * ATM_VSTR + j] = j < kt ? one16 : zero16;
-      if constexpr (SPLIT) Vl[8 * ATM_VSTR + j] = (_Float16)0.0f;
-    }
+    for (int j = tid; j < ATM_KT; j += 64 * ATM_NW) V.store(j, 8, j < kt ? one : zero);   // the ones row
     __syncthreads();
     if (!active) continue;
     // S^T tile = 32 keys x 32 queries; the NEXT tile's MFMAs are issued before this tile's softmax arithmetic
     // so that the matrix pipe works under it
-    auto s_tile = [&](int t, f32x16& s_hi, f32x16& s_lo) {
-      const att_half4 kh = *reinterpret_cast<const att_half4*>(&Kh[(t + l31) * 8 + 4 * half]);
-      const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if constexpr (SPLIT) {
-        const att_half4 kl = *reinterpret_cast<const att_half4*>(&Kl[(t + l31) * 8 + 4 * half]);
-        s_hi = __builtin_amdgcn_mfma_f32_32x32x8f16(kh, qh, zero, 0, 0, 0);  // (C = the inline constant 0)
-        s_lo = __builtin_amdgcn_mfma_f32_32x32x8f16(kh, ql, zero, 0, 0, 0);
-        s_lo = __builtin_amdgcn_mfma_f32_32x32x8f16(kl, qh, s_lo, 0, 0, 0);
-      } else {
-        s_hi = att_mma8<PREC>(kh, qh, zero);
-      }
-    };
-    // one tile's softmax and O += V P from the scores in (s_hi, s_lo)
-    auto pv_tile = [&](int t, const f32x16& s_hi, const f32x16& s_lo) {
+    auto s_tile = [&](int t) { return att_prod8<PREC>(K.a_operand(t), q); };
+    // one tile's softmax and O += V P from the scores in s
+    auto pv_tile = [&](int t, const att_acc<SPLIT>& s) {
       float sv[16];
       float mx = -1e30f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        if constexpr (SPLIT) sv[r] = s_hi[r] + s_lo[r] * (1.0f / 2048.0f);
-        else sv[r] = s_hi[r];
+        sv[r] = s.value(r);
         mx = fmaxf(mx, sv[r]);
       }
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // the query's other 16 keys live in lane ^ 32
@@ -325,71 +251,49 @@ __global__ __launch_bounds__(64 * ATM_NW, DSG_ATM_MINW) void attention_mfma8_ker
       m = mn;
 #pragma unroll
       for (int r = 0; r < 5; ++r) {  // rows 0..3 (+4 half) = the head dims, row 8 (r = 4, half 0) = the denominator
-        o_hi[r] *= sc;
-        if constexpr (SPLIT) o_lo[r] *= sc;
+        o.hi[r] *= sc;
+        if constexpr (SPLIT) o.lo[r] *= sc;
       }
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         // Registers 8 b .. 8 b + 7 are keys {0..3, 8..11} + 4 half of the tile's b-th 16 keys: as the B operand of a
         // 16-deep MFMA step they only need V (the A operand) read in the same key order.
-        att_half8 ph, pl;
+        att_h8<SPLIT> p;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float pv = __builtin_amdgcn_exp2f(sv[8 * b + i] - mn);
-          if constexpr (SPLIT) {
-            const _Float16 a = (_Float16)pv;
-            ph[i] = a;
-            pl[i] = (_Float16)((pv - (float)a) * 2048.0f);
-          } else {
-            ph[i] = att_cvt<PREC>(pv);
-          }
-        }
-        const _Float16* vhp = &Vh[vrow * ATM_VSTR + t + 16 * b + 4 * half];
-        const att_half4 vh0 = *reinterpret_cast<const att_half4*>(vhp), vh1 = *reinterpret_cast<const att_half4*>(vhp + 8);
-        const att_half8 vh = {vh0[0], vh0[1], vh0[2], vh0[3], vh1[0], vh1[1], vh1[2], vh1[3]};
-        if constexpr (SPLIT) {
-          const _Float16* vlp = &Vl[vrow * ATM_VSTR + t + 16 * b + 4 * half];
-          const att_half4 vl0 = *reinterpret_cast<const att_half4*>(vlp), vl1 = *reinterpret_cast<const att_half4*>(vlp + 8);
-          const att_half8 vl = {vl0[0], vl0[1], vl0[2], vl0[3], vl1[0], vl1[1], vl1[2], vl1[3]};
-          o_hi = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, o_hi, 0, 0, 0);
-          o_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, o_lo, 0, 0, 0);
-          o_lo = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, o_lo, 0, 0, 0);
-        } else {
-          o_hi = mma16<(PREC == 0 ? 2 : PREC)>(vh, ph, o_hi);
-        }
+        for (int i = 0; i < 8; ++i) p.set(i, att_split<PREC>(__builtin_amdgcn_exp2f(sv[8 * b + i] - mn)));
+        o = att_prod16<PREC>(V.frag16(vrow, t, b), p, o);
       }
     };
     // two score sets alternate (no register copies): while one tile's arithmetic runs, the other's MFMAs are in flight
-    f32x16 a_hi, a_lo, b_hi, b_lo;
-    s_tile(0, a_hi, a_lo);
+    att_acc<SPLIT> sa = s_tile(0), sb;
     int t = 0;
     for (; t + 64 <= kt; t += 64) {  // (kt % 32 == 0)
-      s_tile(t + 32, b_hi, b_lo);
-      pv_tile(t, a_hi, a_lo);
-      s_tile(min(t + 64, kt - 32), a_hi, a_lo);  // (past the end: a tile that is not used)
-      pv_tile(t + 32, b_hi, b_lo);
+      sb = s_tile(t + 32);
+      pv_tile(t, sa);
+      sa = s_tile(min(t + 64, kt - 32));  // (past the end: a tile that is not used)
+      pv_tile(t + 32, sb);
     }
-    if (t < kt) pv_tile(t, a_hi, a_lo);  // odd tile count
+    if (t < kt) pv_tile(t, sa);  // odd tile count
   }
   if (!active) return;
   // row 8 of the tile (register 4 of the lower half-wave) is the denominator; the upper half-wave fetches it
-  const float den_lo = SPLIT ? o_hi[4] + o_lo[4] * (1.0f / 2048.0f) : o_hi[4];  // (meaningful in the lower half-wave only)
+  const float den_lo = o.value(4);  // (meaningful in the lower half-wave only)
   const float den_x = __shfl_xor(den_lo, 32, 64);
   const float den = half ? den_x : den_lo;
   const float inv = 1.0f / den;
-  float* op = out + ((size_t)n * c + h * 8) * l;
   if (q0 + l31 < l) {
-    if constexpr (BLK) {  // this lane's four head dims of its query: one 16- / 8-byte piece of the token's channel block
-      float o4[4];
+    float o4[4];  // this lane's four head dims of its query
 #pragma unroll
-      for (int r = 0; r < 4; ++r) o4[r] = (SPLIT ? o_hi[r] + o_lo[r] * (1.0f / 2048.0f) : o_hi[r]) * inv;
+    for (int r = 0; r < 4; ++r) o4[r] = o.value(r) * inv;
+    if constexpr (BLK) {  // ... are one 16- / 8-byte piece of the token's channel block
       char* ob = reinterpret_cast<char*>(out) + ((((size_t)n * c + h * 8) * l + (size_t)(q0 + l31) * 8) + 4 * half) * ESZ;
       if constexpr (E16) *reinterpret_cast<att_u2*>(ob) = att_u2{pack2<PREC>(o4[0], o4[1]), pack2<PREC>(o4[2], o4[3])};
       else *reinterpret_cast<float4*>(ob) = make_float4(o4[0], o4[1], o4[2], o4[3]);
-    }
+    } else {
+      float* op = out + ((size_t)n * c + h * 8) * l;
 #pragma unroll
-    for (int r = 0; r < (BLK ? 0 : 4); ++r)
-      op[(size_t)(r + 4 * half) * l + q0 + l31] = (SPLIT ? o_hi[r] + o_lo[r] * (1.0f / 2048.0f) : o_hi[r]) * inv;
+      for (int r = 0; r < 4; ++r) op[(size_t)(r + 4 * half) * l + q0 + l31] = o4[r];
+    }
     if (lse && half == 0) lse[((size_t)n * heads + h) * l + q0 + l31] = m + log2f(den);
   }
 }
@@ -738,16 +642,6 @@ __global__ __launch_bounds__(256) void attention_bwd_dkv_kernel(const float* __r
 //   kernel B (dK, dV): columns = this wave's 32 keys, rows = queries from LDS (with their lse and D):
 //                  S = Q^T K, dP = dO^T V, dV^T += dO(as [d][query]) P, dK^T += Q(as [d][query]) dS
 // ---------------------------------------------------------------------------------------------------
-// (value, (value - hi) * 2^11) as an fp16 pair: the fp16x2 split of the PREC 0 kernels (x == hi + lo * 2^-11 to 2^-22 relative)
-// (a macro: the targets are vector ELEMENTS, which a reference parameter cannot bind to)
-#define ATT_SPLIT(v, hi, lo)                               \
-  do {                                                     \
-    const float sv_ = (v);                                 \
-    const _Float16 sh_ = (_Float16)sv_;                    \
-    (hi) = sh_;                                            \
-    (lo) = (_Float16)((sv_ - (float)sh_) * 2048.0f);       \
-  } while (0)
-
 // PREC 0 (round 6; the fp32 tape's attention backward, training_pipeline.py:86 through the mid block's Attention): every product
 // as the fp16x2 split -- a.b ~ a1.b1 + 2^-11 (a1.b2 + a2.b1), three MFMAs, the cross terms on accumulators of their own -- with
 // dO brought to [1, 2) by a power of two first (the pieces are fp16: unscaled gradients of 1e-6 would land in its subnormals).
@@ -760,120 +654,64 @@ __global__ __launch_bounds__(64 * ATM_NW, 2) void attention_bwd_dq_mfma8_kernel(
                                                                                int heads, int l, float qscale) {
   constexpr bool SPLIT = PREC == 0;
   constexpr bool SCALE = PREC != 1;  // fp16 pieces: dO is brought to [1, 2) by a power of two before it is rounded (see above)
-  __shared__ __attribute__((aligned(16))) _Float16 Kh[ATM_KT * 8], Vk[ATM_KT * 8];   // [key][d]: A operands of S^T and dP^T
-  __shared__ __attribute__((aligned(16))) _Float16 Kd[8 * ATM_VSTR];                  // [d][key]: A operand of dQ^T += K dS
-  __shared__ __attribute__((aligned(16))) _Float16 Kl[SPLIT ? ATM_KT * 8 : 8], Vkl[SPLIT ? ATM_KT * 8 : 8], Kdl[SPLIT ? 8 * ATM_VSTR : 8];
+  __shared__ __attribute__((aligned(16))) _Float16 Kh[ATM_KT * 8], Vh[ATM_KT * 8];   // [key][d]: A operands of S^T and dP^T
+  __shared__ __attribute__((aligned(16))) _Float16 Kdh[8 * ATM_VSTR];                 // [d][key]: A operand of dQ^T += K dS
+  __shared__ __attribute__((aligned(16))) _Float16 Kl[SPLIT ? ATM_KT * 8 : 8], Vl[SPLIT ? ATM_KT * 8 : 8], Kdl[SPLIT ? 8 * ATM_VSTR : 8];
+  const att_image<SPLIT, false> K(Kh, Kl), V(Vh, Vl);
+  const att_image<SPLIT, true> Kd(Kdh, Kdl);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-  const int qtiles = (l + 32 * ATM_NW - 1) / (32 * ATM_NW);
-  int bid = blockIdx.x;
-  if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);  // (a head's tiles behind one L2)
-  const int qt = bid % qtiles, hn = bid / qtiles;
-  const int h = hn % heads, n = hn / heads;
+  const att_tile wg = att_tile_id(l, heads);   // (tile = 32 * ATM_NW queries)
+  const int h = wg.h, n = wg.n;
   const float* qp = qkv + ((size_t)n * 3 * c + h * 8) * l;
   const float* kp = qp + (size_t)c * l;
   const float* vp = kp + (size_t)c * l;
   const size_t obase = ((size_t)n * c + h * 8) * l;
-  const int q0 = (qt * ATM_NW + wave) * 32;
+  const int q0 = (wg.tile * ATM_NW + wave) * 32;
   const bool active = q0 < l;
   const int qi = min(q0 + l31, l - 1);
-  att_half4 qh, dh, ql, dl;
+  att_h4<SPLIT> q, d;
   float dpart = 0.f;
   float dov4[4], amax = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const size_t at = (size_t)(4 * half + i) * l + qi;
     dov4[i] = dout[obase + at];
-    if constexpr (SPLIT) ATT_SPLIT(qp[at] * qscale, qh[i], ql[i]);
-    else qh[i] = att_cvt<PREC>(qp[at] * qscale);
+    q.set(i, att_split<PREC>(qp[at] * qscale));
     dpart = fmaf(dov4[i], o[obase + at], dpart);
     amax = fmaxf(amax, fabsf(dov4[i]));
   }
   // this query's power-of-two scale (lanes l31 and l31 + 32 hold its two halves): dQ_i is linear in dO_i, undone at the end
   float qs = 1.f, qs_inv = 1.f;
-  if constexpr (SCALE) {
-    amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
-    if (amax > 0.f && amax < 3.0e38f) {
-      int ex;
-      (void)frexpf(amax, &ex);
-      qs = ldexpf(1.0f, 1 - ex);
-      qs_inv = ldexpf(1.0f, ex - 1);
-    }
-  }
+  if constexpr (SCALE) att_pow2_scale(fmaxf(amax, __shfl_xor(amax, 32, 64)), &qs, &qs_inv);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if constexpr (SPLIT) ATT_SPLIT(dov4[i] * qs, dh[i], dl[i]);
-    else dh[i] = att_cvt<PREC>(dov4[i] * qs);
-  }
+  for (int i = 0; i < 4; ++i) d.set(i, att_split<PREC>(dov4[i] * qs));
   const float dd_true = dpart + __shfl_xor(dpart, 32, 64);   // D = rowsum(dO * O) of this lane's query
   const float dd = dd_true * qs;
   const float ls = lse[((size_t)n * heads + h) * l + qi];
-  f32x16 dq, dq_lo;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) dq[r] = dq_lo[r] = 0.f;
+  att_acc<SPLIT> dq = {};
   const int vrow = min(l31, 7);
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int j0 = 0; j0 < l; j0 += ATM_KT) {
     const int kt = min(ATM_KT, l - j0);
     __syncthreads();
-    for (int e = tid; e < 8 * ATM_KT; e += 64 * ATM_NW) {
-      const int i = e / ATM_KT, j = e - i * ATM_KT;  // coalesced along the keys
-      float kv = 0.f, vv = 0.f;
-      if (j < kt) {
-        kv = kp[(size_t)i * l + j0 + j];
-        vv = vp[(size_t)i * l + j0 + j];
-      }
-      if constexpr (SPLIT) {
-        _Float16 kh16, kl16, vh16, vl16;
-        ATT_SPLIT(kv, kh16, kl16);
-        ATT_SPLIT(vv, vh16, vl16);
-        Kh[j * 8 + i] = kh16; Kl[j * 8 + i] = kl16;
-        Kd[i * ATM_VSTR + j] = kh16; Kdl[i * ATM_VSTR + j] = kl16;
-        Vk[j * 8 + i] = vh16; Vkl[j * 8 + i] = vl16;
-      } else {
-        Kh[j * 8 + i] = att_cvt<PREC>(kv);
-        Kd[i * ATM_VSTR + j] = att_cvt<PREC>(kv);
-        Vk[j * 8 + i] = att_cvt<PREC>(vv);
-      }
-    }
+    att_stage<PREC>(kp, 1.f, vp, 1.f, l, j0, kt, [&](int j, int i, att_h1<SPLIT> k, att_h1<SPLIT> v) {
+      K.store(j, i, k);
+      Kd.store(j, i, k);
+      V.store(j, i, v);
+    });
     __syncthreads();
     if (!active) continue;
     for (int t = 0; t < kt; t += 32) {
-      const att_half4 ka = *reinterpret_cast<const att_half4*>(&Kh[(t + l31) * 8 + 4 * half]);
-      const att_half4 va = *reinterpret_cast<const att_half4*>(&Vk[(t + l31) * 8 + 4 * half]);
-      f32x16 sc = att_mma8<PREC>(ka, qh, zero);   // S^T: rows = keys, this lane's column = its query
-      f32x16 dp = att_mma8<PREC>(va, dh, zero);   // dP^T
-      if constexpr (SPLIT) {
-        const att_half4 kal = *reinterpret_cast<const att_half4*>(&Kl[(t + l31) * 8 + 4 * half]);
-        const att_half4 val = *reinterpret_cast<const att_half4*>(&Vkl[(t + l31) * 8 + 4 * half]);
-        f32x16 s2 = att_mma8<PREC>(ka, ql, zero), p2 = att_mma8<PREC>(va, dl, zero);
-        s2 = att_mma8<PREC>(kal, qh, s2);
-        p2 = att_mma8<PREC>(val, dh, p2);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          sc[r] += s2[r] * (1.0f / 2048.0f);
-          dp[r] += p2[r] * (1.0f / 2048.0f);
-        }
-      }
+      const att_acc<SPLIT> sc = att_prod8<PREC>(K.a_operand(t), q);   // S^T: rows = keys, this lane's column = its query
+      const att_acc<SPLIT> dp = att_prod8<PREC>(V.a_operand(t), d);   // dP^T
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
-        att_half8 dsh, dsl;
+        att_h8<SPLIT> ds;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const float pv = __builtin_amdgcn_exp2f(sc[8 * b + i] - ls);
-          if constexpr (SPLIT) ATT_SPLIT(pv * (dp[8 * b + i] - dd), dsh[i], dsl[i]);
-          else dsh[i] = att_cvt<PREC>(pv * (dp[8 * b + i] - dd));
+          const float pv = __builtin_amdgcn_exp2f(sc.value(8 * b + i) - ls);
+          ds.set(i, att_split<PREC>(pv * (dp.value(8 * b + i) - dd)));
         }
-        const _Float16* kdp = &Kd[vrow * ATM_VSTR + t + 16 * b + 4 * half];
-        const att_half4 k0 = *reinterpret_cast<const att_half4*>(kdp), k1 = *reinterpret_cast<const att_half4*>(kdp + 8);
-        const att_half8 kd = {k0[0], k0[1], k0[2], k0[3], k1[0], k1[1], k1[2], k1[3]};
-        dq = mma16<PREC>(kd, dsh, dq);
-        if constexpr (SPLIT) {
-          const _Float16* klp = &Kdl[vrow * ATM_VSTR + t + 16 * b + 4 * half];
-          const att_half4 m0 = *reinterpret_cast<const att_half4*>(klp), m1 = *reinterpret_cast<const att_half4*>(klp + 8);
-          const att_half8 kdl = {m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-          dq_lo = mma16<PREC>(kd, dsl, dq_lo);
-          dq_lo = mma16<PREC>(kdl, dsh, dq_lo);
-        }
+        dq = att_prod16<PREC>(Kd.frag16(vrow, t, b), ds, dq);
       }
     }
   }
@@ -881,8 +719,7 @@ __global__ __launch_bounds__(64 * ATM_NW, 2) void attention_bwd_dq_mfma8_kernel(
   const float sm = qscale * 0.6931471805599453f * qs_inv;  // qscale = log2(e)/sqrt(D); the softmax scale alone is 1/sqrt(D)
   float* dqp = dqkv + ((size_t)n * 3 * c + h * 8) * l;
 #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    dqp[(size_t)(r + 4 * half) * l + q0 + l31] = (SPLIT ? dq[r] + dq_lo[r] * (1.0f / 2048.0f) : dq[r]) * sm;
+  for (int r = 0; r < 4; ++r) dqp[(size_t)(r + 4 * half) * l + q0 + l31] = dq.value(r) * sm;
   if (half == 0) dsum[((size_t)n * heads + h) * l + q0 + l31] = dd_true;
 }
 
@@ -894,34 +731,28 @@ __global__ __launch_bounds__(64 * ATM_NW, PREC == 0 ? 1 : 2) void attention_bwd_
   constexpr bool SPLIT = PREC == 0;  // fp32-class: every product as the fp16x2 split (see the dq kernel)
   constexpr bool SCALE = PREC != 1;  // fp16 pieces: dO is brought to [1, 2) by a power of two before it is rounded (see above)
   __shared__ __attribute__((aligned(16))) _Float16 Qh[ATM_KT * 8], Gh[ATM_KT * 8];            // [query][d]: A operands of S and dP
-  __shared__ __attribute__((aligned(16))) _Float16 Qd[8 * ATM_VSTR], Gd[8 * ATM_VSTR];        // [d][query]: A operands of dK^T, dV^T
+  __shared__ __attribute__((aligned(16))) _Float16 Qdh[8 * ATM_VSTR], Gdh[8 * ATM_VSTR];      // [d][query]: A operands of dK^T, dV^T
   __shared__ __attribute__((aligned(16))) _Float16 Ql[SPLIT ? ATM_KT * 8 : 8], Gl[SPLIT ? ATM_KT * 8 : 8];
   __shared__ __attribute__((aligned(16))) _Float16 Qdl[SPLIT ? 8 * ATM_VSTR : 8], Gdl[SPLIT ? 8 * ATM_VSTR : 8];
   __shared__ __attribute__((aligned(16))) float Ls[ATM_KT], Ds[ATM_KT];                        // lse and D of the tile's queries
+  const att_image<SPLIT, false> Q(Qh, Ql), G(Gh, Gl);
+  const att_image<SPLIT, true> Qd(Qdh, Qdl), Gd(Gdh, Gdl);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-  const int ktiles = (l + 32 * ATM_NW - 1) / (32 * ATM_NW);
-  int bid = blockIdx.x;
-  if ((gridDim.x & 7) == 0) bid = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int kt_i = bid % ktiles, hn = bid / ktiles;
-  const int h = hn % heads, n = hn / heads;
+  const att_tile wg = att_tile_id(l, heads);   // (tile = 32 * ATM_NW keys)
+  const int h = wg.h, n = wg.n;
   const float* qp = qkv + ((size_t)n * 3 * c + h * 8) * l;
   const float* kp = qp + (size_t)c * l;
   const float* vp = kp + (size_t)c * l;
   const size_t obase = ((size_t)n * c + h * 8) * l;
   const size_t lbase = ((size_t)n * heads + h) * l;
-  const int k0 = (kt_i * ATM_NW + wave) * 32;
+  const int k0 = (wg.tile * ATM_NW + wave) * 32;
   const bool active = k0 < l;
   const int ki = min(k0 + l31, l - 1);
-  att_half4 kh, vh, kl, vl;
+  att_h4<SPLIT> k, v;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    if constexpr (SPLIT) {
-      ATT_SPLIT(kp[(size_t)(4 * half + i) * l + ki], kh[i], kl[i]);
-      ATT_SPLIT(vp[(size_t)(4 * half + i) * l + ki], vh[i], vl[i]);
-    } else {
-      kh[i] = att_cvt<PREC>(kp[(size_t)(4 * half + i) * l + ki]);
-      vh[i] = att_cvt<PREC>(vp[(size_t)(4 * half + i) * l + ki]);
-    }
+    k.set(i, att_split<PREC>(kp[(size_t)(4 * half + i) * l + ki]));
+    v.set(i, att_split<PREC>(vp[(size_t)(4 * half + i) * l + ki]));
   }
   // dK_j and dV_j sum over the queries: ONE scale for the head's whole dO (its 8 l values are contiguous; every workgroup of
   // the head finds the same maximum -- no atomics, no extra buffer); rows far below the maximum lose bits that do not show in the sum
@@ -937,44 +768,19 @@ __global__ __launch_bounds__(64 * ATM_NW, PREC == 0 ? 1 : 2) void attention_bwd_
     m = wmax[0];
 #pragma unroll
     for (int w = 1; w < ATM_NW; ++w) m = fmaxf(m, wmax[w]);
-    if (m > 0.f && m < 3.0e38f) {
-      int ex;
-      (void)frexpf(m, &ex);
-      gs = ldexpf(1.0f, 1 - ex);
-      gs_inv = ldexpf(1.0f, ex - 1);
-    }
+    att_pow2_scale(m, &gs, &gs_inv);
   }
-  f32x16 dk, dv, dk_lo, dv_lo;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) dk[r] = dv[r] = dk_lo[r] = dv_lo[r] = 0.f;
+  att_acc<SPLIT> dk = {}, dv = {};
   const int vrow = min(l31, 7);
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int j0 = 0; j0 < l; j0 += ATM_KT) {
     const int qt = min(ATM_KT, l - j0);
     __syncthreads();
-    for (int e = tid; e < 8 * ATM_KT; e += 64 * ATM_NW) {
-      const int i = e / ATM_KT, j = e - i * ATM_KT;  // coalesced along the queries
-      float qv = 0.f, gv = 0.f;
-      if (j < qt) {
-        qv = qp[(size_t)i * l + j0 + j] * qscale;
-        gv = dout[obase + (size_t)i * l + j0 + j] * gs;
-      }
-      if constexpr (SPLIT) {
-        _Float16 q1, q2, g1, g2;
-        ATT_SPLIT(qv, q1, q2);
-        ATT_SPLIT(gv, g1, g2);
-        Qh[j * 8 + i] = q1; Ql[j * 8 + i] = q2;
-        Qd[i * ATM_VSTR + j] = q1; Qdl[i * ATM_VSTR + j] = q2;
-        Gh[j * 8 + i] = g1; Gl[j * 8 + i] = g2;
-        Gd[i * ATM_VSTR + j] = g1; Gdl[i * ATM_VSTR + j] = g2;
-      } else {
-        const _Float16 gb = att_cvt<PREC>(gv);
-        Qh[j * 8 + i] = att_cvt<PREC>(qv);
-        Qd[i * ATM_VSTR + j] = att_cvt<PREC>(qv);
-        Gh[j * 8 + i] = gb;
-        Gd[i * ATM_VSTR + j] = gb;
-      }
-    }
+    att_stage<PREC>(qp, qscale, dout + obase, gs, l, j0, qt, [&](int j, int i, att_h1<SPLIT> q, att_h1<SPLIT> g) {
+      Q.store(j, i, q);
+      Qd.store(j, i, q);
+      G.store(j, i, g);
+      Gd.store(j, i, g);
+    });
     for (int j = tid; j < ATM_KT; j += 64 * ATM_NW) {
       Ls[j] = j < qt ? lse[lbase + j0 + j] : 0.f;
       Ds[j] = j < qt ? dsum[lbase + j0 + j] * gs : 0.f;
@@ -982,22 +788,8 @@ __global__ __launch_bounds__(64 * ATM_NW, PREC == 0 ? 1 : 2) void attention_bwd_
     __syncthreads();
     if (!active) continue;
     for (int t = 0; t < qt; t += 32) {
-      const att_half4 qa = *reinterpret_cast<const att_half4*>(&Qh[(t + l31) * 8 + 4 * half]);
-      const att_half4 ga = *reinterpret_cast<const att_half4*>(&Gh[(t + l31) * 8 + 4 * half]);
-      f32x16 sc = att_mma8<PREC>(qa, kh, zero);   // S: rows = queries, this lane's column = its key
-      f32x16 dp = att_mma8<PREC>(ga, vh, zero);   // dP
-      if constexpr (SPLIT) {
-        const att_half4 qal = *reinterpret_cast<const att_half4*>(&Ql[(t + l31) * 8 + 4 * half]);
-        const att_half4 gal = *reinterpret_cast<const att_half4*>(&Gl[(t + l31) * 8 + 4 * half]);
-        f32x16 s2 = att_mma8<PREC>(qa, kl, zero), p2 = att_mma8<PREC>(ga, vl, zero);
-        s2 = att_mma8<PREC>(qal, kh, s2);
-        p2 = att_mma8<PREC>(gal, vh, p2);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          sc[r] += s2[r] * (1.0f / 2048.0f);
-          dp[r] += p2[r] * (1.0f / 2048.0f);
-        }
-      }
+      const att_acc<SPLIT> sc = att_prod8<PREC>(Q.a_operand(t), k);   // S: rows = queries, this lane's column = its key
+      const att_acc<SPLIT> dp = att_prod8<PREC>(G.a_operand(t), v);   // dP
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         // registers 8b .. 8b + 7 = queries t + 16 b + 4 half + {0..3, 8..11}
@@ -1007,38 +799,15 @@ __global__ __launch_bounds__(64 * ATM_NW, PREC == 0 ? 1 : 2) void attention_bwd_
         const float4 d1 = *reinterpret_cast<const float4*>(&Ds[t + 16 * b + 4 * half + 8]);
         const float lsr[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
         const float ddr[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-        att_half8 ph, dsh, pl, dsl;
+        att_h8<SPLIT> p, ds;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const float pv = __builtin_amdgcn_exp2f(sc[8 * b + i] - lsr[i]);
-          if constexpr (SPLIT) {
-            ATT_SPLIT(pv, ph[i], pl[i]);
-            ATT_SPLIT(pv * (dp[8 * b + i] - ddr[i]), dsh[i], dsl[i]);
-          } else {
-            ph[i] = att_cvt<PREC>(pv);
-            dsh[i] = att_cvt<PREC>(pv * (dp[8 * b + i] - ddr[i]));
-          }
+          const float pv = __builtin_amdgcn_exp2f(sc.value(8 * b + i) - lsr[i]);
+          p.set(i, att_split<PREC>(pv));
+          ds.set(i, att_split<PREC>(pv * (dp.value(8 * b + i) - ddr[i])));
         }
-        const _Float16* gdp = &Gd[vrow * ATM_VSTR + t + 16 * b + 4 * half];
-        const _Float16* qdp = &Qd[vrow * ATM_VSTR + t + 16 * b + 4 * half];
-        const att_half4 g0 = *reinterpret_cast<const att_half4*>(gdp), g1 = *reinterpret_cast<const att_half4*>(gdp + 8);
-        const att_half4 x0 = *reinterpret_cast<const att_half4*>(qdp), x1 = *reinterpret_cast<const att_half4*>(qdp + 8);
-        const att_half8 gd = {g0[0], g0[1], g0[2], g0[3], g1[0], g1[1], g1[2], g1[3]};
-        const att_half8 qd = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-        dv = mma16<PREC>(gd, ph, dv);
-        dk = mma16<PREC>(qd, dsh, dk);
-        if constexpr (SPLIT) {
-          const _Float16* glp = &Gdl[vrow * ATM_VSTR + t + 16 * b + 4 * half];
-          const _Float16* qlp = &Qdl[vrow * ATM_VSTR + t + 16 * b + 4 * half];
-          const att_half4 h0 = *reinterpret_cast<const att_half4*>(glp), h1 = *reinterpret_cast<const att_half4*>(glp + 8);
-          const att_half4 y0 = *reinterpret_cast<const att_half4*>(qlp), y1 = *reinterpret_cast<const att_half4*>(qlp + 8);
-          const att_half8 gdl = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-          const att_half8 qdl = {y0[0], y0[1], y0[2], y0[3], y1[0], y1[1], y1[2], y1[3]};
-          dv_lo = mma16<PREC>(gd, pl, dv_lo);
-          dv_lo = mma16<PREC>(gdl, ph, dv_lo);
-          dk_lo = mma16<PREC>(qd, dsl, dk_lo);
-          dk_lo = mma16<PREC>(qdl, dsh, dk_lo);
-        }
+        dv = att_prod16<PREC>(Gd.frag16(vrow, t, b), p, dv);
+        dk = att_prod16<PREC>(Qd.frag16(vrow, t, b), ds, dk);
       }
     }
   }
@@ -1047,9 +816,8 @@ __global__ __launch_bounds__(64 * ATM_NW, PREC == 0 ? 1 : 2) void attention_bwd_
   float* dvp = dkp + (size_t)c * l;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const float dkr = SPLIT ? dk[r] + dk_lo[r] * (1.0f / 2048.0f) : dk[r], dvr = SPLIT ? dv[r] + dv_lo[r] * (1.0f / 2048.0f) : dv[r];
-    dkp[(size_t)(r + 4 * half) * l + k0 + l31] = dkr * (0.6931471805599453f * gs_inv);  // (q came pre-scaled by log2(e)/sqrt(D))
-    dvp[(size_t)(r + 4 * half) * l + k0 + l31] = dvr * gs_inv;
+    dkp[(size_t)(r + 4 * half) * l + k0 + l31] = dk.value(r) * (0.6931471805599453f * gs_inv);  // (q came pre-scaled by log2(e)/sqrt(D))
+    dvp[(size_t)(r + 4 * half) * l + k0 + l31] = dv.value(r) * gs_inv;
   }
 }
 

@@ -120,6 +120,7 @@ def test_groupnorm(c0, c1, groups, hw):
                                          (1, 64, 2, 64),
                                          (1, 16, 2, 2048),   # head_dim 8: two LDS key tiles on the matrix-core kernel
                                          (2, 24, 3, 96),     # ... a partial key tile, a query block with idle waves
+                                         (1, 16, 2, 544),    # ... a full and a partial key tile, idle waves in the last block
                                          (1, 8, 1, 100)])    # ... l % 32 != 0: the VALU kernel
 def test_attention(n, c, heads, l):
     qkv = _t(31, (n, 3 * c, l), 1.5)
@@ -132,7 +133,7 @@ def test_attention(n, c, heads, l):
 
 
 @pytest.mark.parametrize("mode", ["fp32", "bf16", "fp16"])
-@pytest.mark.parametrize("n,c,heads,l", [(2, 512, 64, 1024), (1, 16, 2, 2048), (2, 24, 3, 96)])
+@pytest.mark.parametrize("n,c,heads,l", [(2, 512, 64, 1024), (1, 16, 2, 2048), (2, 24, 3, 96), (1, 16, 2, 544)])
 def test_attention_blocked_layout(n, c, heads, l, mode):
     """dsg_attention_fwd_blocked: q, k, v and the output channel-blocked (head_dim 8 = one channel block), the layout the
     plan keeps between the q/k/v projection, the attention core and the out-projection.  fp32: the SAME arithmetic as the

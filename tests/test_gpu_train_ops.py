@@ -118,7 +118,9 @@ def test_attention_backward(n, c, heads, l):
 
 
 @pytest.mark.parametrize("mode", ["bf16", "fp16"])
-@pytest.mark.parametrize("n,c,heads,l", [(2, 64, 8, 1024), (3, 512, 64, 1024), (1, 32, 4, 256)])
+@pytest.mark.parametrize("n,c,heads,l", [(2, 64, 8, 1024), (3, 512, 64, 1024), (1, 32, 4, 256),
+                                         (1, 16, 2, 544),   # 512 + 32 keys, a last query tile with one active wave; 6 workgroups
+                                         (1, 64, 8, 544)])  # ... 24 workgroups: the same partial tiles under the XCD permutation
 def test_attention_backward_bf16_matrix_cores(n, c, heads, l, mode):
     """dsg_attention_bwd_dt(DSG_BF16 / DSG_F16): head_dim 8 on the matrix cores with q, k, v, dO, P, dS rounded once to 16 bits
     (the mixed-precision tapes; tiny gradients included: dO ~ 1e-6 as without a loss scale).  Against torch autograd in fp64."""
@@ -143,7 +145,8 @@ def test_attention_backward_bf16_matrix_cores(n, c, heads, l, mode):
     assert float((exact - ref).norm() / ref.norm()) <= 1e-5
 
 
-@pytest.mark.parametrize("n,c,heads,l,mag", [(2, 64, 8, 1024, 1.0), (3, 512, 64, 1024, 1.0), (1, 32, 4, 256, 1e-6), (2, 64, 8, 96, 30.0)])
+@pytest.mark.parametrize("n,c,heads,l,mag", [(2, 64, 8, 1024, 1.0), (3, 512, 64, 1024, 1.0), (1, 32, 4, 256, 1e-6), (2, 64, 8, 96, 30.0),
+                                             (1, 16, 2, 544, 1.0), (1, 64, 8, 544, 1.0)])   # (partial second tile, see above)
 def test_attention_backward_fp32_on_the_matrix_cores_is_in_the_valu_kernels_class(n, c, heads, l, mag):
     """Round 6: `dsg_attention_bwd` (the fp32 tape; training_pipeline.py:86 through the mid block's Attention) runs head_dim 8 on the
     matrix cores with every product as an fp16x2 split (three MFMAs, dO scaled to [1, 2) by a power of two first) instead of the
