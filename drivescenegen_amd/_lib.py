@@ -131,6 +131,9 @@ _vp, _i32, _i64, _f32, _sz, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, 
 DSG_F32, DSG_BF16, DSG_F16 = 0, 1, 2
 DTYPE_CODES = {"fp32": DSG_F32, "bf16": DSG_BF16, "fp16": DSG_F16}
 TORCH_DTYPES = {DSG_F32: torch.float32, DSG_BF16: torch.bfloat16, DSG_F16: torch.float16}
+# dsg_pred_type (include/dsg.h): what the network's output stands for, by diffusers' `prediction_type` name
+DSG_PRED_EPSILON, DSG_PRED_SAMPLE, DSG_PRED_V = 0, 1, 2
+PRED_CODES = {"epsilon": DSG_PRED_EPSILON, "sample": DSG_PRED_SAMPLE, "v_prediction": DSG_PRED_V}
 
 # name -> argtypes; every function returns int32 status unless noted.  This table is the single
 # Python-side statement of the ABI; tests/test_abi.py checks it against include/dsg.h.
@@ -197,6 +200,10 @@ SIGNATURES = {
     "dsg_add_noise_philox": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, C.c_uint64, C.c_uint64, _vp],
     "dsg_ddpm_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
     "dsg_ddim_step": [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _vp],
+    "dsg_ddpm_step_pt": [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
+    "dsg_ddim_step_pt": [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _vp],
+    "dsg_add_noise_target": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp],
+    "dsg_add_noise_target_philox": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, C.c_uint64, C.c_uint64, _vp],
     "dsg_dynthresh_workspace_bytes": [_i32, C.POINTER(_sz)],
     "dsg_dynthresh_scale": [_vp, _vp, _vp, _i32, _i64, _f32, _f32, _i64, _i64, _f32, _f32, _vp, _sz, _vp],
     "dsg_ddpm_step_thr": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _f32, _vp],
@@ -230,6 +237,7 @@ SIGNATURES = {
     "dsg_silu_fwd": [_vp, _i64, _vp, _vp],
     "dsg_silu_bwd": [_vp, _vp, _i64, _vp, _vp],
     "dsg_mse_loss": [_vp, _vp, _i64, _f32, _vp, _vp, _vp, _sz, _vp],
+    "dsg_mse_loss_weighted": [_vp, _vp, _vp, _i32, _i64, _f32, _vp, _vp, _vp, _sz, _vp],
     "dsg_l2_norm": [_vp, _i64, _vp, _vp, _sz, _vp],
     "dsg_clip_scale": [_vp, _i64, _vp, _f32, _vp],
     "dsg_adamw_step": [_vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _vp, _f32, _vp],

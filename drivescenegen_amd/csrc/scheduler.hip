@@ -4,13 +4,15 @@
 // DDIMScheduler.step (reference call sites: DriveSceneGen/pipeline/training_pipeline.py:80
 // `noise_scheduler.add_noise`, and the DDPMPipeline loop behind training_pipeline.py:26-32 and
 // DriveSceneGen/scripts/generation.py:14-20; formulas SURVEY.md App. A.3 / A.3b / A.4), and adds the samplers diffusers ships
-// next to them: RePaint, DPM-Solver++ multistep, dynamic thresholding.
+// next to them: RePaint, DPM-Solver++ multistep, dynamic thresholding, and the sample- / v-prediction forms of the DDPM / DDIM
+// step with the training target that goes with them.
 // Every expression is evaluated with individually rounded fp32 operations in the reference's
 // order (fma contraction disabled for this file, IEEE division), so results are bit-identical to torch-CPU.
 //
 // The file reads: per-element formulas (each operation order stated ONCE) -> the training / headline kernels (add_noise, philox,
 // ddpm_step, ddim_step: one loop each, untouched by the sampler features) -> the quad skeleton ("one lane owns four consecutive
-// elements") and the four sampler kernels built on it -> the thresholding quantile -> postprocess -> host helpers -> entry points.
+// elements") and the sampler kernels built on it (RePaint, DPM-Solver++, the prediction-type step, the training target, the
+// thresholded step) -> the thresholding quantile -> postprocess -> host helpers -> entry points.
 #include <type_traits>
 
 #include "dsg_common.h"
@@ -50,6 +52,37 @@ __device__ __forceinline__ float ddpm_add_noise(float r, float sigma, float z) {
 
 // DDIM: prev = sap*p0 + dc*e
 __device__ __forceinline__ float ddim_combine(float p0, float e, float sap, float dc) { return axpby(sap, p0, dc, e); }
+
+// a*x - b*z: two multiplies, one subtract (the data prediction of a v-predicting network; the velocity target)
+__device__ __forceinline__ float axmby(float a, float x, float b, float z) {
+  return __fsub_rn(__fmul_rn(a, x), __fmul_rn(b, z));
+}
+
+// What the network's output m stands for (DSG_PRED_*, include/dsg.h) decides how a step gets its data prediction p0 and its
+// noise prediction pe:
+//   epsilon   p0 = pred_x0(x, m)            pe = m
+//   sample    p0 = m                        pe = (x - sa*m) / sb        (sb == 0: IEEE division by zero, as diffusers at abar = 1)
+//   v         p0 = sa*x - sb*m              pe = sa*m + sb*x
+// p0 is clamped to +-clip when clip > 0; pe is taken from the UNCLAMPED inputs and never recomputed from the clamped p0
+// (diffusers' use_clipped_model_output=False, the only mode).
+template <int PRED>
+__device__ __forceinline__ float pred_p0(float x, float m, float sb, float sa, float clip) {
+  if (PRED == DSG_PRED_EPSILON) return pred_x0(x, m, sb, sa, clip);
+  float v = PRED == DSG_PRED_SAMPLE ? m : axmby(sa, x, sb, m);
+  if (clip > 0.f) v = clampf(v, -clip, clip);
+  return v;
+}
+template <int PRED>
+__device__ __forceinline__ float pred_eps(float x, float m, float sb, float sa) {
+  if (PRED == DSG_PRED_EPSILON) return m;
+  if (PRED == DSG_PRED_SAMPLE) return __fdiv_rn(__fsub_rn(x, __fmul_rn(sa, m)), sb);
+  // axpby(sa, m, sb, x), with one product pinned in a register of its own (as in repaint_elem below: hipcc otherwise pairs the
+  // four products of p0 and pe into v_pk_mul_f32 and sums a pair with v_pk_add_f32 ... op_sel:[0,1], the form
+  // tests/test_isa_policy.py bans; same arithmetic, same rounding)
+  float am = __fmul_rn(sa, m);
+  asm volatile("" : "+v"(am));
+  return __fadd_rn(am, __fmul_rn(sb, x));
+}
 
 // grid = (ceil(per_sample/1024), n)
 __global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict__ x0, const float* __restrict__ nz,
@@ -251,6 +284,19 @@ __device__ __forceinline__ void noise4(const float* __restrict__ nz, float* __re
   if (noise_out) store4(noise_out, q << 2, numel, vec, z);
 }
 
+// Per-sample values (a [numel / per] table: the thresholding scales, add_noise's coefficients) of the quad from flat index e on:
+// one division when its elements share a sample (then the quad is whole).  tbl is read at index < numel / per only: an element
+// past numel gets `past`.
+__device__ __forceinline__ void per_sample4(const float* __restrict__ tbl, int64_t e, int64_t numel, int64_t per, float past,
+                                            float (&s)[4]) {
+  const int64_t n = e / per, rem = e - n * per;
+  if (rem + 4 <= per) {
+    s[0] = s[1] = s[2] = s[3] = tbl[n];
+  } else {                                          // the quad crosses into the next sample(s), or past the end
+    for (int j = 0; j < 4; ++j) s[j] = e + j < numel ? tbl[(e + j) / per] : past;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // RePaint (Lugmayr et al., CVPR 2022, Algorithm 1; diffusers' RePaintScheduler.step / .undo_step): scene completion with an
 // unconditional network.  One pass per reverse step, per element and in THIS order (include/dsg.h states it as the contract):
@@ -389,6 +435,63 @@ __global__ __launch_bounds__(256) void dpmsolver_step_kernel(const float* __rest
     for (int j = 0; j < 4; ++j) dpm_elem<ORDER, NOISE != NOISE_NONE>(xv[j], ev[j], av[j], bv[j], z[j], k, r[j], m[j]);
     store4(prev, e, numel, vec, r);
     store4(m0_out, e, numel, vec, m);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The DDPM / DDIM step of a network that predicts epsilon, the sample or v (Salimans & Ho, "Progressive Distillation for Fast
+// Sampling of Diffusion Models", 2022; diffusers' `prediction_type`).  One pass, per element (include/dsg.h states it as the
+// contract): p0 = pred_p0<PRED>, then
+//   MODE 0, DDPM:  prev = c0*p0 + ct*x  [+ sigma*z]      (a = c0, b = ct, c = sigma; NOISE_READ when the step has a noise term)
+//   MODE 1, DDIM:  prev = sap*p0 + dc*pe                 (a = sap, b = dc; pe = pred_eps<PRED>; NOISE_NONE)
+// With PRED == DSG_PRED_EPSILON these are ddpm_step_kernel's / ddim_step_kernel's bits.
+template <int MODE, int PRED, int NOISE, bool VEC>
+__global__ __launch_bounds__(256) void pt_step_kernel(const float* __restrict__ x, const float* __restrict__ mo,
+                                                      const float* __restrict__ nz, float* __restrict__ prev, int64_t numel,
+                                                      float sb, float sa, float clip, float a, float b, float c) {
+  static_assert(NOISE != NOISE_PHILOX && (MODE == 0 || NOISE == NOISE_NONE), "these steps read their noise or have none");
+  for_each_quad(numel, [&](int64_t q, int64_t e) {
+    const bool vec = quad_is_vec<VEC>(e, numel);
+    float xv[4], mv[4], z[4], r[4];
+    load4(x, e, numel, vec, xv);
+    load4(mo, e, numel, vec, mv);
+    noise4<NOISE>(nz, nullptr, q, numel, vec, philox_words{}, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float p0 = pred_p0<PRED>(xv[j], mv[j], sb, sa, clip);
+      r[j] = MODE == 1 ? ddim_combine(p0, pred_eps<PRED>(xv[j], mv[j], sb, sa), a, b) : ddpm_combine(p0, xv[j], a, b);
+      if (NOISE != NOISE_NONE) r[j] = ddpm_add_noise(r[j], c, z[j]);
+    }
+    store4(prev, e, numel, vec, r);
+  });
+}
+
+// The training step's x_t and its velocity target in one pass over (x0, z):  noisy = sa[n]*x0 + sb[n]*z (add_noise_kernel's
+// bits), target = sa[n]*z - sb[n]*x0, n the sample of the ELEMENT (a quad may straddle two samples when per % 4 != 0).
+// z: NOISE_READ, or NOISE_PHILOX -- the stream of philox_kernel.  Either output may be NULL (the same in every lane).
+template <int NOISE, bool VEC>
+__global__ __launch_bounds__(256) void noise_target_kernel(const float* __restrict__ x0, const float* __restrict__ nz,
+                                                           const float* __restrict__ sa, const float* __restrict__ sb,
+                                                           float* __restrict__ noisy, float* __restrict__ target, int64_t numel,
+                                                           int64_t per, philox_words w) {
+  static_assert(NOISE != NOISE_NONE, "the forward process has a noise term");
+  for_each_quad(numel, [&](int64_t q, int64_t e) {
+    const bool vec = quad_is_vec<VEC>(e, numel);
+    float xv[4], z[4], a[4], b[4], r[4];
+    load4(x0, e, numel, vec, xv);
+    noise4<NOISE>(nz, nullptr, q, numel, vec, w, z);
+    per_sample4(sa, e, numel, per, 0.f, a);
+    per_sample4(sb, e, numel, per, 0.f, b);
+    if (noisy) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = axpby(a[j], xv[j], b[j], z[j]);
+      store4(noisy, e, numel, vec, r);
+    }
+    if (target) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = axmby(a[j], z[j], b[j], xv[j]);
+      store4(target, e, numel, vec, r);
+    }
   });
 }
 
@@ -565,17 +668,6 @@ __global__ __launch_bounds__(256) void thr_scan_kernel(uint32_t* __restrict__ ws
   }
 }
 
-// The scales of the quad from flat index e on: one division when its elements share a sample (then the quad is whole).
-// thr is read at index < numel / per only: an element past numel gets the scale 1.
-__device__ __forceinline__ void thr_scales4(const float* __restrict__ thr, int64_t e, int64_t numel, int64_t per, float (&s)[4]) {
-  const int64_t n = e / per, rem = e - n * per;
-  if (rem + 4 <= per) {
-    s[0] = s[1] = s[2] = s[3] = thr[n];
-  } else {                                          // the quad crosses into the next sample(s), or past the end
-    for (int j = 0; j < 4; ++j) s[j] = e + j < numel ? thr[(e + j) / per] : 1.f;
-  }
-}
-
 // The DDPM / DDIM step with the thresholded data prediction.
 // MODE 0: DDPM (ddpm_combine: a = c0, b = ct, c = sigma; NOISE_READ when the step has a noise term);  1: DDIM (ddim_combine:
 // a = sap, b = dc; NOISE_NONE)
@@ -591,7 +683,7 @@ __global__ __launch_bounds__(256) void thr_step_kernel(const float* __restrict__
     load4(x, e, numel, vec, xv);
     load4(eps, e, numel, vec, ev);
     noise4<NOISE>(nz, nullptr, q, numel, vec, philox_words{}, z);
-    thr_scales4(thr, e, numel, per, s);
+    per_sample4(thr, e, numel, per, 1.f, s);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float p0 = thr_x0(xv[j], ev[j], sb, sa, s[j]);
@@ -838,6 +930,90 @@ DSG_API int dsg_ddim_step_thr(const float* sample, const float* eps, const float
                               float dir_coef, void* stream) {
   return dsg::thr_step<1>("dsg_ddim_step_thr", sample, eps, nullptr, thr, prev, numel, per_sample, sqrt_beta_prod_t,
                           sqrt_alpha_prod_t, sqrt_alpha_prev, dir_coef, 0.f, stream);
+}
+
+namespace dsg {
+// both prediction-type steps: the checks, then pt_step_kernel<MODE, pred_type, noise ? NOISE_READ : NOISE_NONE, every pointer aligned>
+template <int MODE>
+static int pt_step(const char* who, const float* sample, const float* model_out, const float* noise, float* prev, int64_t numel,
+                   int32_t pred_type, float sb, float sa, float clip, float a, float b, float c, void* stream) {
+  if (!(sample && model_out && prev)) return fail(DSG_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  if (numel <= 0) return fail(DSG_ERR_INVALID_ARG, "%s: numel must be positive", who);
+  if (pred_type < DSG_PRED_EPSILON || pred_type > DSG_PRED_V)
+    return fail(DSG_ERR_INVALID_ARG, "%s: pred_type=%d is not DSG_PRED_EPSILON, DSG_PRED_SAMPLE or DSG_PRED_V", who, pred_type);
+  const uint64_t bytes = (uint64_t)numel * sizeof(float);
+  const void* ins[3] = {sample, model_out, noise};
+  for (int i = 0; i < 3; ++i)
+    if (overlaps2(prev, bytes, ins[i], bytes)) return fail(DSG_ERR_INVALID_ARG, "%s: prev overlaps an input (input %d)", who, i);
+  const dim3 grid(quad_blocks(numel)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  with_constant<3>(pred_type, [&](auto PRED) {
+    with_constant<2>(noise != nullptr, [&](auto NZ) {
+      with_constant<2>(all_aligned16(sample, model_out, noise, prev), [&](auto VEC) {
+        // (NOISE_READ exists for the DDPM form only: MODE 1 is always called without noise)
+        hipLaunchKernelGGL((pt_step_kernel<MODE, DSG_CONST(PRED), MODE == 0 ? DSG_CONST(NZ) : NOISE_NONE, DSG_CONST(VEC) != 0>), grid,
+                           block, 0, st, sample, model_out, noise, prev, numel, sb, sa, clip, a, b, c);
+      });
+    });
+  });
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
+
+// both training-target entries: the checks, then noise_target_kernel<noise ? NOISE_READ : NOISE_PHILOX, every pointer aligned>
+static int noise_target(const char* who, const float* x0, const float* noise, const float* sa, const float* sb, float* noisy,
+                        float* target, int32_t n, int64_t per, uint64_t seed, uint64_t offset, void* stream) {
+  if (!(x0 && sa && sb)) return fail(DSG_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  if (!noisy && !target) return fail(DSG_ERR_INVALID_ARG, "%s: noisy and target are both NULL", who);
+  if (n <= 0 || per <= 0) return fail(DSG_ERR_INVALID_ARG, "%s: bad dims (n=%d per_sample=%lld)", who, n, (long long)per);
+  const int64_t numel = (int64_t)n * per;
+  const uint64_t bytes = (uint64_t)numel * sizeof(float), tbl = (uint64_t)n * sizeof(float);
+  const void* ins[4] = {x0, noise, sa, sb};
+  const uint64_t in_bytes[4] = {bytes, bytes, tbl, tbl};
+  float* outs[2] = {noisy, target};
+  for (int o = 0; o < 2; ++o)
+    for (int i = 0; i < 4; ++i)
+      if (overlaps2(outs[o], bytes, ins[i], in_bytes[i]))
+        return fail(DSG_ERR_INVALID_ARG, "%s: an output overlaps an input (output %d, input %d)", who, o, i);
+  if (overlaps2(noisy, bytes, target, bytes)) return fail(DSG_ERR_INVALID_ARG, "%s: noisy overlaps target", who);
+  const dim3 grid(quad_blocks(numel)), block(256);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const philox_words w = philox_words::of(seed, offset);
+  with_constant<2>(noise == nullptr, [&](auto PHILOX) {
+    with_constant<2>(all_aligned16(x0, noise, noisy, target), [&](auto VEC) {
+      hipLaunchKernelGGL((noise_target_kernel<NOISE_READ + DSG_CONST(PHILOX), DSG_CONST(VEC) != 0>), grid, block, 0, st, x0, noise,
+                         sa, sb, noisy, target, numel, per, w);
+    });
+  });
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
+}  // namespace dsg
+
+DSG_API int dsg_ddpm_step_pt(const float* sample, const float* model_out, const float* noise, float* prev, int64_t numel,
+                             int32_t pred_type, float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float clip, float coef_x0,
+                             float coef_xt, float sigma, void* stream) {
+  return dsg::pt_step<0>("dsg_ddpm_step_pt", sample, model_out, noise, prev, numel, pred_type, sqrt_beta_prod_t, sqrt_alpha_prod_t,
+                         clip, coef_x0, coef_xt, sigma, stream);
+}
+
+DSG_API int dsg_ddim_step_pt(const float* sample, const float* model_out, float* prev, int64_t numel, int32_t pred_type,
+                             float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float clip, float sqrt_alpha_prev, float dir_coef,
+                             void* stream) {
+  return dsg::pt_step<1>("dsg_ddim_step_pt", sample, model_out, nullptr, prev, numel, pred_type, sqrt_beta_prod_t,
+                         sqrt_alpha_prod_t, clip, sqrt_alpha_prev, dir_coef, 0.f, stream);
+}
+
+DSG_API int dsg_add_noise_target(const float* x0, const float* noise, const float* sqrt_a, const float* sqrt_1ma, float* noisy,
+                                 float* target, int32_t n, int64_t per_sample, void* stream) {
+  DSG_CHECK_ARG(noise, "dsg_add_noise_target: NULL pointer");
+  return dsg::noise_target("dsg_add_noise_target", x0, noise, sqrt_a, sqrt_1ma, noisy, target, n, per_sample, 0, 0, stream);
+}
+
+DSG_API int dsg_add_noise_target_philox(const float* x0, const float* sqrt_a, const float* sqrt_1ma, float* noisy, float* target,
+                                        int32_t n, int64_t per_sample, uint64_t seed, uint64_t offset, void* stream) {
+  return dsg::noise_target("dsg_add_noise_target_philox", x0, nullptr, sqrt_a, sqrt_1ma, noisy, target, n, per_sample, seed,
+                           offset, stream);
 }
 
 DSG_API int dsg_repaint_step(const dsg_repaint_step_args* a, void* stream) {

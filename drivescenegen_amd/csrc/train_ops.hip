@@ -336,6 +336,34 @@ __global__ __launch_bounds__(256) void sqdiff_partial_kernel(const float* __rest
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
+// The per-sample weighted form of sqdiff_partial_kernel (min-SNR loss weighting): partial[b] = sum over the block's grid-stride
+// slice of w[n] * (a-b)^2, n = i / per the element's sample; optionally dpred = (coef * w[n]) * (a - b).  The same slices, the
+// same order and the same double sums as sqdiff_partial_kernel, so all w == 1 gives its bits.  The sample index is carried
+// along the grid-stride walk (stride = sq * per + sr, from the host) instead of divided out per element.
+__global__ __launch_bounds__(256) void sqdiff_weighted_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                      const float* __restrict__ w, int64_t numel, int64_t per,
+                                                                      int64_t sq, int64_t sr, float coef,
+                                                                      float* __restrict__ dpred, double* __restrict__ partial) {
+  double s = 0.0, z = 0.0;
+  const int64_t i0 = blockIdx.x * (int64_t)256 + threadIdx.x;
+  int64_t n = i0 / per, r = i0 - n * per;
+  for (int64_t i = i0; i < numel; i += (int64_t)gridDim.x * 256) {
+    const float wn = w[n];
+    const float d = a[i] - b[i];
+    const double dd = (double)d * d;
+    s += (double)wn * dd;
+    if (dpred) dpred[i] = (coef * wn) * d;
+    n += sq;
+    r += sr;
+    if (r >= per) {
+      r -= per;
+      ++n;
+    }
+  }
+  block_sum2(s, z);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
 // out[0] = scale * sum(partial) (mode 0) or sqrt(sum(partial)) (mode 1); fixed order -> deterministic
 __global__ void finish_sum_kernel(const double* __restrict__ partial, int nb, double scale, int mode,
                                   float* __restrict__ out) {
@@ -1057,6 +1085,24 @@ DSG_API int dsg_mse_loss(const float* pred, const float* target, int64_t numel, 
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(dsg::sqdiff_partial_kernel, dim3(nb), dim3(256), 0, st, pred, target, numel,
                      2.0f * grad_scale / (float)numel, dpred, ws);
+  DSG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dsg::finish_sum_kernel, dim3(1), dim3(64), 0, st, ws, nb, 1.0 / (double)numel, 0, loss);
+  DSG_LAUNCH_CHECK();
+  return DSG_OK;
+}
+
+DSG_API int dsg_mse_loss_weighted(const float* pred, const float* target, const float* w, int32_t n, int64_t per_sample,
+                                  float grad_scale, float* loss, float* dpred, double* ws, size_t ws_bytes, void* stream) {
+  DSG_CHECK_ARG(pred && target && w && loss && ws, "dsg_mse_loss_weighted: NULL pointer");
+  DSG_CHECK_ARG(n > 0 && per_sample > 0, "dsg_mse_loss_weighted: bad dims (n=%d per_sample=%lld)", n, (long long)per_sample);
+  const int64_t numel = (int64_t)n * per_sample;
+  const int nb = dsg::stream_blocks2(numel);
+  if (ws_bytes < (size_t)nb * sizeof(double))
+    return dsg::fail(DSG_ERR_WORKSPACE_TOO_SMALL, "dsg_mse_loss_weighted: workspace %zu < %zu", ws_bytes, (size_t)nb * 8);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t stride = (int64_t)nb * 256;
+  hipLaunchKernelGGL(dsg::sqdiff_weighted_partial_kernel, dim3(nb), dim3(256), 0, st, pred, target, w, numel, per_sample,
+                     stride / per_sample, stride % per_sample, 2.0f * grad_scale / (float)numel, dpred, ws);
   DSG_LAUNCH_CHECK();
   hipLaunchKernelGGL(dsg::finish_sum_kernel, dim3(1), dim3(64), 0, st, ws, nb, 1.0 / (double)numel, 0, loss);
   DSG_LAUNCH_CHECK();

@@ -836,6 +836,23 @@ def mse_loss(pred, target, grad_scale=1.0, need_grad=True):
     return loss, dpred
 
 
+def mse_loss_weighted(pred, target, weights, grad_scale=1.0, need_grad=True):
+    """(loss [1] fp32 device tensor, dpred or None): mean over all elements of weights[n] * (pred - target)^2, `weights` one
+    fp32 value per leading-dim sample, and its gradient * grad_scale (``dsg_mse_loss_weighted``)."""
+    n = int(pred.shape[0])
+    if weights.dtype != torch.float32 or weights.numel() != n or weights.device != pred.device:
+        raise ValueError(f"mse_loss_weighted: weights must be {n} fp32 values on {pred.device}")
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if need_grad else None
+    ws = _reduce_ws(pred.device)
+    with torch.cuda.device(pred.device):
+        _lib.check(_lib.load().dsg_mse_loss_weighted(_lib.ptr(pred.contiguous()), _lib.ptr(target.contiguous()),
+                                                    _lib.ptr(weights.contiguous().view(-1)), n, pred.numel() // n,
+                                                    float(grad_scale), _lib.ptr(loss), _lib.ptr(dpred), _lib.ptr(ws),
+                                                    ws.numel() * 8, _st(pred)))
+    return loss, dpred
+
+
 def l2_norm(x):
     out = torch.empty(1, dtype=torch.float32, device=x.device)
     ws = _reduce_ws(x.device)

@@ -11,7 +11,13 @@ Formulas: SURVEY.md App. A.3 / A.3b.
 Host side (this file): the beta / alpha-bar tables, the integer timestep tables and the per-step fp32
 scalars, computed with the same fp32 operation order as the reference so they are bit-identical.
 Device side: the elementwise tensor math, in libdsg.so (dsg_add_noise / dsg_ddpm_step / dsg_ddim_step / dsg_repaint_step /
-dsg_repaint_undo / dsg_dpmsolver_step; with ``thresholding=True``: dsg_dynthresh_scale + dsg_ddpm_step_thr / dsg_ddim_step_thr).
+dsg_repaint_undo / dsg_dpmsolver_step; with ``thresholding=True``: dsg_dynthresh_scale + dsg_ddpm_step_thr / dsg_ddim_step_thr;
+with ``prediction_type`` "sample" / "v_prediction": dsg_ddpm_step_pt / dsg_ddim_step_pt, and dsg_add_noise_target for the
+training target).
+
+Which config values a class runs is ONE table per class, ``_choices``: DDPM and DDIM take the three beta schedules, the three
+prediction types and the three timestep spacings of diffusers 0.20.0 (DDIM also ``rescale_betas_zero_snr``); RePaint and
+DPM-Solver++ stay on linear betas and epsilon prediction.
 
 Layout: ``_SchedulerBase`` holds what all four classes share (config handling, the tables, ``add_noise``, config I/O, the
 memo helper); ``_Thresholding`` is the dynamic-thresholding mixin of DDPM and DDIM; ``_NoiseSource`` is the device-noise switch
@@ -21,6 +27,7 @@ decides where the noise comes from, checks its shape and makes it contiguous fp3
 from __future__ import annotations
 
 import json
+import math
 import os
 from types import SimpleNamespace
 from typing import NamedTuple, Optional
@@ -110,7 +117,8 @@ class _SchedulerBase:
     config_name = "scheduler_config.json"
     order = 1
     _defaults = {}
-    _fixed_keys = ()        # config keys this engine runs at their default value only
+    _choices = {}           # config key -> the values this class runs; any other value raises (a key not listed is free)
+    _named_by_diffusers = ()    # keys of _choices whose unknown values diffusers itself rejects with a ValueError
 
     def __init__(self, **kwargs):
         cfg = dict(self._defaults)
@@ -118,14 +126,16 @@ class _SchedulerBase:
         if unknown:
             raise TypeError(f"{self._class_name}: unexpected arguments {sorted(unknown)}")
         cfg.update(kwargs)
-        for key in self._fixed_keys:
-            if key in cfg and cfg[key] != self._defaults[key]:
-                raise NotImplementedError(f"{self._class_name}: {key}={cfg[key]!r} is outside the DriveSceneGen "
-                                          f"path (supported: {self._defaults[key]!r})")
+        for key, allowed in self._choices.items():
+            v = cfg[key]
+            if isinstance(v, bool) != isinstance(allowed[0], bool) or v not in allowed:
+                error = ValueError if key in self._named_by_diffusers else NotImplementedError
+                raise error(f"{self._class_name}: {key}={v!r} is outside the DriveSceneGen path "
+                            f"(supported: {allowed[0] if len(allowed) == 1 else allowed!r})")
         self._check_extra(cfg)
         self.config = FrozenConfig(**cfg)
         n = cfg["num_train_timesteps"]
-        self.betas = torch.linspace(cfg["beta_start"], cfg["beta_end"], n, dtype=torch.float32)
+        self.betas = self._betas(cfg)
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self.one = torch.tensor(1.0)
@@ -135,9 +145,23 @@ class _SchedulerBase:
         self.timesteps = torch.from_numpy(np.arange(0, n)[::-1].copy())
         self._dev_tables = {}
         self._scalar_cache = {}
+        self._snr_tables = {}
 
     def _check_extra(self, cfg):
         """The class's own refusals, on the merged config."""
+
+    def _betas(self, cfg):
+        """The fp32 beta table of ``beta_schedule``, in diffusers' operation order."""
+        n, schedule = cfg["num_train_timesteps"], cfg["beta_schedule"]
+        if schedule == "linear":
+            return torch.linspace(cfg["beta_start"], cfg["beta_end"], n, dtype=torch.float32)
+        if schedule == "scaled_linear":
+            return torch.linspace(cfg["beta_start"] ** 0.5, cfg["beta_end"] ** 0.5, n, dtype=torch.float32) ** 2
+        if schedule == "squaredcos_cap_v2":     # (Nichol & Dhariwal's cosine alpha-bar, in Python doubles)
+            def alpha_bar(t):
+                return math.cos((t + 0.008) / 1.008 * math.pi / 2) ** 2
+            return torch.tensor([min(1 - alpha_bar((i + 1) / n) / alpha_bar(i / n), 0.999) for i in range(n)], dtype=torch.float32)
+        raise NotImplementedError(f"{self._class_name}: beta_schedule={schedule!r}")
 
     @staticmethod
     def _memo(cache, key, make):
@@ -212,6 +236,72 @@ class _SchedulerBase:
                                                        int(offset) & (2 ** 64 - 1), _lib.stream_ptr(x0.device)))
         return noisy, noise
 
+    # ---- the velocity target of a v-predicting network ------------------------------------------------------------
+    def _noise_target(self, who, x0, noise, timesteps, want_noisy, seed=0, offset=0):
+        """(noisy or None, target) of ``dsg_add_noise_target`` (`noise` a tensor) / ``dsg_add_noise_target_philox`` (`noise`
+        None: the Philox tensor (seed, offset)): one pass over (x0, noise); the timestep rules are ``add_noise``'s."""
+        if not x0.is_cuda or x0.dtype != torch.float32:
+            raise RuntimeError(f"DDPMScheduler.{who} runs on the MI355X HIP engine only (an fp32 GPU tensor)")
+        sa_t, sb_t = self._sqrt_tables(x0.device)
+        t = timesteps.to(x0.device).flatten()
+        n = t.numel()
+        if x0.dim() == 0 or (n != 1 and n != x0.shape[0]):
+            raise ValueError(f"{who}: timesteps must have one entry per leading-dim sample (or one entry)")
+        sa, sb = sa_t[t].contiguous(), sb_t[t].contiguous()
+        x0c = x0.contiguous()
+        noisy, target = (torch.empty_like(x0c) if want_noisy else None), torch.empty_like(x0c)
+        lib, st, per = _lib.load(), _lib.stream_ptr(x0.device), x0c.numel() // n
+        with torch.cuda.device(x0.device):
+            if noise is not None:
+                if tuple(noise.shape) != tuple(x0.shape):
+                    raise ValueError(f"{who}: noise has shape {tuple(noise.shape)}, the sample {tuple(x0.shape)}")
+                nz = noise.to(x0.device, x0.dtype).contiguous()
+                _lib.check(lib.dsg_add_noise_target(_lib.ptr(x0c), _lib.ptr(nz), _lib.ptr(sa), _lib.ptr(sb), _lib.ptr(noisy),
+                                                    _lib.ptr(target), n, per, st))
+            else:
+                _lib.check(lib.dsg_add_noise_target_philox(_lib.ptr(x0c), _lib.ptr(sa), _lib.ptr(sb), _lib.ptr(noisy),
+                                                           _lib.ptr(target), n, per, int(seed) & (2 ** 64 - 1),
+                                                           int(offset) & (2 ** 64 - 1), st))
+        return noisy, target
+
+    def get_velocity(self, sample, noise, timesteps):
+        """diffusers' ``get_velocity``: v = sqrt(abar_t)*noise - sqrt(1 - abar_t)*sample, the target of a network trained with
+        ``prediction_type="v_prediction"`` (Salimans & Ho, 2022)."""
+        return self._noise_target("get_velocity", sample, noise, timesteps, want_noisy=False)[1]
+
+    def add_noise_velocity(self, original_samples, noise, timesteps):
+        """(noisy, velocity): ``add_noise`` and ``get_velocity`` as ONE pass over (x0, noise); both bitwise the single calls."""
+        return self._noise_target("add_noise_velocity", original_samples, noise, timesteps, want_noisy=True)
+
+    def add_noise_velocity_device(self, original_samples, timesteps, seed: int, offset: int):
+        """(noisy, velocity) for the Philox noise tensor (seed, offset) of ``add_noise_device``, which is made in the kernel and
+        not written: `noisy` is bitwise ``add_noise_device``'s, `velocity` bitwise ``get_velocity`` of that noise."""
+        return self._noise_target("add_noise_velocity_device", original_samples, None, timesteps, True, seed, offset)
+
+    # ---- min-SNR-gamma loss weights (Hang et al., "Efficient Diffusion Training via Min-SNR Weighting Strategy", 2023) ------
+    def snr_weights(self, gamma: float, device=None):
+        """The per-timestep loss weight, fp32 [num_train_timesteps] on `device` (cached; index it with the step's timesteps):
+        min(snr, gamma) / snr for an epsilon-predicting network, / (snr + 1) for v-prediction, min(snr, gamma) itself for
+        sample prediction; snr = (sqrt(abar) / sqrt(1 - abar))^2 in fp32."""
+        gamma = float(gamma)
+        if not gamma > 0.0:
+            raise ValueError(f"{self._class_name}.snr_weights: gamma={gamma!r} must be positive")
+        pred = self.config.get("prediction_type", "epsilon")
+
+        def make():
+            ac = self.alphas_cumprod
+            snr = (torch.sqrt(ac) / torch.sqrt(1 - ac)) ** 2
+            w = torch.clamp(snr, max=gamma)
+            if pred == "epsilon":
+                if bool((snr == 0).any()):
+                    raise ValueError(f"{self._class_name}.snr_weights: a zero-terminal-SNR table has no epsilon weight (0 / 0); "
+                                     "train it with prediction_type='v_prediction' or 'sample'")
+                w = w / snr
+            elif pred == "v_prediction":
+                w = w / (snr + 1)
+            return w.to(device) if device is not None else w
+        return self._memo(self._snr_tables, (gamma, pred, str(device)), make)
+
     # ---- config I/O (App. A.5) ----------------------------------------------------------------------
     def save_pretrained(self, save_directory):
         os.makedirs(save_directory, exist_ok=True)
@@ -257,6 +347,11 @@ class _Thresholding:
             raise ValueError(f"{self._class_name}: dynamic_thresholding_ratio={q!r} is outside [0, 1]")
         if isinstance(m, bool) or not isinstance(m, (int, float, np.integer, np.floating)) or not 1.0 <= m < float("inf"):
             raise ValueError(f"{self._class_name}: sample_max_value={m!r} is not a finite number >= 1")
+        if cfg["thresholding"]:     # (dsg_dynthresh_scale ranks the epsilon form of p0; the tables it was checked on are these)
+            for key in ("prediction_type", "beta_schedule", "timestep_spacing"):
+                if cfg[key] != self._defaults[key]:
+                    raise NotImplementedError(f"{self._class_name}: {key}={cfg[key]!r} with thresholding=True is outside the "
+                                              f"DriveSceneGen path (supported: {self._defaults[key]!r})")
 
     def threshold_ranks(self, per: int):
         """(k_lo, k_hi, w) of the ``dynamic_thresholding_ratio`` quantile of `per` values, as torch.quantile forms them: the
@@ -307,11 +402,12 @@ class DDPMScheduler(_Thresholding, _SchedulerBase):
                      trained_betas=None, variance_type="fixed_small", clip_sample=True, prediction_type="epsilon",
                      thresholding=False, dynamic_thresholding_ratio=0.995, clip_sample_range=1.0,
                      sample_max_value=1.0, timestep_spacing="leading", steps_offset=0)
-    _fixed_keys = ("beta_schedule", "trained_betas", "prediction_type", "timestep_spacing")
+    _choices = dict(beta_schedule=("linear", "scaled_linear", "squaredcos_cap_v2"), trained_betas=(None,),
+                    variance_type=("fixed_small",), prediction_type=("epsilon", "sample", "v_prediction"),
+                    timestep_spacing=("leading", "linspace", "trailing"))
+    _named_by_diffusers = ("prediction_type",)
 
     def _check_extra(self, cfg):
-        if cfg["variance_type"] != "fixed_small":
-            raise NotImplementedError("DDPMScheduler: only variance_type='fixed_small' (the reference default)")
         self._check_thresholding(cfg)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
@@ -319,9 +415,15 @@ class DDPMScheduler(_Thresholding, _SchedulerBase):
         if num_inference_steps > n_train:
             raise ValueError(f"num_inference_steps {num_inference_steps} > num_train_timesteps {n_train}")
         self.num_inference_steps = num_inference_steps
-        ratio = n_train // num_inference_steps  # integer floor: 1000 // 750 == 1 (SURVEY headline finding 4)
-        ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
-        ts += self.config.steps_offset
+        spacing = self.config.get("timestep_spacing", "leading")
+        if spacing == "leading":
+            ratio = n_train // num_inference_steps  # integer floor: 1000 // 750 == 1 (SURVEY headline finding 4)
+            ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
+            ts += self.config.steps_offset
+        elif spacing == "linspace":
+            ts = np.linspace(0, n_train - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
+        else:       # "trailing": the table starts at the LAST training timestep (Lin et al., 2023, section 3.2)
+            ts = (np.round(np.arange(n_train, 0, -n_train / num_inference_steps)) - 1).astype(np.int64)
         self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
 
     def previous_timestep(self, t: int) -> int:
@@ -348,6 +450,13 @@ class DDPMScheduler(_Thresholding, _SchedulerBase):
         return dict(sqrt_beta_prod_t=float(b_t ** 0.5), sqrt_alpha_prod_t=float(a_t ** 0.5), coef_x0=float(c0),
                     coef_xt=float(ct), sigma=float(var ** 0.5))
 
+    @staticmethod
+    def _check_pt_inputs(who, sample, model_output):
+        if sample.dtype != torch.float32 or model_output.dtype != torch.float32:
+            raise ValueError(f"{who}: fp32 only")
+        if tuple(model_output.shape) != tuple(sample.shape):
+            raise ValueError(f"{who}: model output {tuple(model_output.shape)} != sample {tuple(sample.shape)}")
+
     def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True, variance_noise=None):
         if not sample.is_cuda:
             raise RuntimeError("DDPMScheduler.step runs on the MI355X HIP engine only (got a CPU tensor)")
@@ -364,10 +473,16 @@ class DDPMScheduler(_Thresholding, _SchedulerBase):
                 _lib.check(_lib.load().dsg_ddpm_step_thr(_lib.ptr(x), _lib.ptr(e), nz.ptr, _lib.ptr(scale), _lib.ptr(prev),
                                                         x.numel(), per, s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"],
                                                         s["coef_x0"], s["coef_xt"], s["sigma"], _lib.stream_ptr(x.device)))
-            else:
+            elif self.config.prediction_type == "epsilon":
                 _lib.check(_lib.load().dsg_ddpm_step(_lib.ptr(x), _lib.ptr(e), nz.ptr, _lib.ptr(prev), x.numel(),
                                                     s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"], clip, s["coef_x0"],
                                                     s["coef_xt"], s["sigma"], _lib.stream_ptr(x.device)))
+            else:
+                self._check_pt_inputs("DDPMScheduler.step", x, e)
+                _lib.check(_lib.load().dsg_ddpm_step_pt(_lib.ptr(x), _lib.ptr(e), nz.ptr, _lib.ptr(prev), x.numel(),
+                                                       _lib.PRED_CODES[self.config.prediction_type], s["sqrt_beta_prod_t"],
+                                                       s["sqrt_alpha_prod_t"], clip, s["coef_x0"], s["coef_xt"], s["sigma"],
+                                                       _lib.stream_ptr(x.device)))
             _record_consumed(nz, x.device)
         if not return_dict:
             return (prev,)
@@ -381,11 +496,28 @@ class DDIMScheduler(DDPMScheduler):
                      prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
                      clip_sample_range=1.0, sample_max_value=1.0, timestep_spacing="leading",
                      rescale_betas_zero_snr=False)
+    _choices = dict(beta_schedule=("linear", "scaled_linear", "squaredcos_cap_v2"), trained_betas=(None,),
+                    prediction_type=("epsilon", "sample", "v_prediction"), timestep_spacing=("leading", "linspace", "trailing"),
+                    rescale_betas_zero_snr=(False, True))
 
     def _check_extra(self, cfg):
-        if cfg["rescale_betas_zero_snr"]:
-            raise NotImplementedError("DDIMScheduler: rescale_betas_zero_snr is outside the DriveSceneGen path")
         self._check_thresholding(cfg)
+        if cfg["thresholding"] and cfg["rescale_betas_zero_snr"]:
+            raise NotImplementedError("DDIMScheduler: rescale_betas_zero_snr=True with thresholding=True is outside the "
+                                      "DriveSceneGen path (supported: False)")
+
+    def _betas(self, cfg):
+        betas = super()._betas(cfg)
+        if not cfg.get("rescale_betas_zero_snr", False):
+            return betas
+        # diffusers' rescale_zero_terminal_snr (Lin et al., 2023, Algorithm 1) in fp32: shift sqrt(abar) so that its last entry
+        # is exactly 0, scale so that its first entry is unchanged
+        s = torch.cumprod(1.0 - betas, dim=0).sqrt()
+        a0, aT = s[0].clone(), s[-1].clone()
+        s -= aT
+        s *= a0 / (a0 - aT)
+        ab = s ** 2
+        return 1 - torch.cat([ab[0:1], ab[1:] / ab[:-1]])
 
     def __init__(self, **kwargs):
         super().__init__(**kwargs)
@@ -425,10 +557,16 @@ class DDIMScheduler(DDPMScheduler):
                 _lib.check(_lib.load().dsg_ddim_step_thr(_lib.ptr(x), _lib.ptr(e), _lib.ptr(scale), _lib.ptr(prev), x.numel(),
                                                         per, s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"],
                                                         s["sqrt_alpha_prev"], s["dir_coef"], _lib.stream_ptr(x.device)))
-            else:
+            elif self.config.prediction_type == "epsilon":
                 _lib.check(_lib.load().dsg_ddim_step(_lib.ptr(x), _lib.ptr(e), _lib.ptr(prev), x.numel(),
                                                     s["sqrt_beta_prod_t"], s["sqrt_alpha_prod_t"], clip,
                                                     s["sqrt_alpha_prev"], s["dir_coef"], _lib.stream_ptr(x.device)))
+            else:
+                self._check_pt_inputs("DDIMScheduler.step", x, e)
+                _lib.check(_lib.load().dsg_ddim_step_pt(_lib.ptr(x), _lib.ptr(e), _lib.ptr(prev), x.numel(),
+                                                       _lib.PRED_CODES[self.config.prediction_type], s["sqrt_beta_prod_t"],
+                                                       s["sqrt_alpha_prod_t"], clip, s["sqrt_alpha_prev"], s["dir_coef"],
+                                                       _lib.stream_ptr(x.device)))
         if eta > 0:
             z = variance_noise if variance_noise is not None else _randn_like_reference(
                 model_output.shape, generator, model_output.device, model_output.dtype)
@@ -501,7 +639,8 @@ class RePaintScheduler(DDIMScheduler, _NoiseSource):
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", eta=0.0,
                      trained_betas=None, clip_sample=True)
     # (diffusers' RePaintScheduler has no thresholding keys: passing one is an unexpected argument, and its step never thresholds)
-    _fixed_keys = ("beta_schedule", "trained_betas")
+    _choices = dict(beta_schedule=("linear",), trained_betas=(None,))
+    _named_by_diffusers = ()
 
     def _check_extra(self, cfg):
         pass
@@ -646,18 +785,13 @@ class DPMSolverMultistepScheduler(_SchedulerBase, _NoiseSource):
                      sample_max_value=1.0, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
                      use_karras_sigmas=False, lambda_min_clipped=-float("inf"), variance_type=None,
                      timestep_spacing="linspace", steps_offset=0)
-    _fixed_keys = ("beta_schedule", "trained_betas", "prediction_type", "thresholding", "dynamic_thresholding_ratio",
-                   "sample_max_value", "use_karras_sigmas", "lambda_min_clipped")
-    _choices = dict(solver_order=(1, 2, 3), algorithm_type=("dpmsolver++", "sde-dpmsolver++"), solver_type=("midpoint", "heun"),
+    _choices = dict(beta_schedule=("linear",), trained_betas=(None,), prediction_type=("epsilon",), thresholding=(False,),
+                    dynamic_thresholding_ratio=(0.995,), sample_max_value=(1.0,), use_karras_sigmas=(False,),
+                    lambda_min_clipped=(-float("inf"),), solver_order=(1, 2, 3), algorithm_type=("dpmsolver++", "sde-dpmsolver++"), solver_type=("midpoint", "heun"),
                     lower_order_final=(True, False), timestep_spacing=("linspace", "leading", "trailing"),
                     variance_type=(None, "fixed_small", "fixed_large"))
 
     def _check_extra(self, cfg):
-        for key, allowed in self._choices.items():
-            v = cfg[key]
-            if isinstance(v, bool) != isinstance(allowed[0], bool) or v not in allowed:
-                raise NotImplementedError(f"{self._class_name}: {key}={v!r} is outside the DriveSceneGen path "
-                                          f"(supported: {allowed!r})")
         if isinstance(cfg["steps_offset"], bool) or not isinstance(cfg["steps_offset"], (int, np.integer)):
             raise NotImplementedError(f"{self._class_name}: steps_offset={cfg['steps_offset']!r} is outside the DriveSceneGen "
                                       "path (supported: an integer)")

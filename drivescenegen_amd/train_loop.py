@@ -1,4 +1,5 @@
-"""End-to-end training driver on the engine's objects: epochs of DDPM epsilon-prediction steps, a seeded sample PNG and a
+"""End-to-end training driver on the engine's objects: epochs of DDPM training steps (epsilon prediction as the reference has
+it; sample / v-prediction and min-SNR loss weighting when the scheduler's config and ``snr_gamma`` ask), a seeded sample PNG and a
 diffusers-layout checkpoint at the configured epoch intervals.
 
 What it stands in for: the reference's driver, /root/reference/DriveSceneGen/pipeline/training_pipeline.py
@@ -141,23 +142,37 @@ class DeviceNoise:
         return off
 
 
-def train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=None, ema=None):
+def train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=None, ema=None, snr_gamma=None):
     """One optimisation step on a clean batch [B, C, H, W] in [-1, 1]; returns the detached loss (a device scalar).
     `noise`: the step's N(0,1) tensor on the batch's device when the caller drew it ahead (``NoiseAhead``); a
     ``DeviceNoise`` for the opt-in library generator; drawn here, on the host, otherwise -- the reference's own order.
     `ema`: an ``EMAModel`` averaged after every optimizer step (one launch), where diffusers' train_unconditional.py calls
-    ``ema_model.step(model.parameters())`` -- on synchronising steps only, a step the fp16 GradScaler skipped included."""
+    ``ema_model.step(model.parameters())`` -- on synchronising steps only, a step the fp16 GradScaler skipped included.
+    The target follows the scheduler's ``prediction_type``: the noise (the reference), the clean batch ("sample") or the
+    velocity ("v_prediction": made in the same pass as x_t).  `snr_gamma`: min-SNR-gamma loss weighting (Hang et al., 2023;
+    5 is the paper's value) with the scheduler's ``snr_weights`` table; None is the reference's unweighted loss."""
+    prediction = noise_scheduler.config.get("prediction_type", "epsilon")
+    velocity = prediction == "v_prediction"
     t = None
     if isinstance(noise, DeviceNoise):
         t = torch.randint(0, noise_scheduler.num_train_timesteps, (batch.shape[0],), device=batch.device).long()
-        noisy, noise = noise_scheduler.add_noise_device(batch, t, noise.seed, noise.next_offset())
+        if velocity:
+            noisy, target = noise_scheduler.add_noise_velocity_device(batch, t, noise.seed, noise.next_offset())
+        else:
+            noisy, target = noise_scheduler.add_noise_device(batch, t, noise.seed, noise.next_offset())
     else:
         if noise is None:
             noise = torch.randn(batch.shape).to(batch.device)
         t = torch.randint(0, noise_scheduler.num_train_timesteps, (batch.shape[0],), device=batch.device).long()
-        noisy = noise_scheduler.add_noise(batch, noise, t).to(torch.float)
+        if velocity:
+            noisy, target = noise_scheduler.add_noise_velocity(batch, noise, t)
+        else:
+            noisy, target = noise_scheduler.add_noise(batch, noise, t).to(torch.float), noise
+    if prediction == "sample":
+        target = batch
+    weights = None if snr_gamma is None else noise_scheduler.snr_weights(snr_gamma, batch.device)[t]
     with accelerator.accumulate(model):
-        loss = mse_loss(model(noisy, t, return_dict=False)[0], noise)
+        loss = mse_loss(model(noisy, t, return_dict=False)[0], target, weights)
         accelerator.backward(loss)
         accelerator.clip_grad_norm_(model.parameters(), 1.0)
         optimizer.step()
@@ -188,24 +203,26 @@ def batches_with_noise(batches, overlap_noise: bool = True):
 
 
 def train_steps(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batches, overlap_noise: bool = True,
-                noise="host", ema=None):
+                noise="host", ema=None, snr_gamma=None):
     """Generator over one pass of `batches` (an epoch's loader): yields each step's detached loss.  Batch k+1 is fetched and
     its noise draw handed to the worker thread before step k's kernels are queued, so the host draw overlaps the GPU.
     ``noise="device"`` (or a ``DeviceNoise``): the library's counter-based generator instead of the host draw (opt-in).
-    `ema`: see ``train_step``."""
+    `ema`, `snr_gamma`: see ``train_step``."""
     if noise != "host":
         gen = noise if isinstance(noise, DeviceNoise) else DeviceNoise(rank=getattr(accelerator, "process_index", 0))
         if noise != "device" and not isinstance(noise, DeviceNoise):
             raise ValueError(f"train_steps: noise must be 'host', 'device' or a DeviceNoise (got {noise!r})")
         for batch in batches:
-            yield train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=gen, ema=ema)
+            yield train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=gen, ema=ema,
+                             snr_gamma=snr_gamma)
         return
     for batch, nz in batches_with_noise(batches, overlap_noise):
-        yield train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=nz, ema=ema)
+        yield train_step(accelerator, model, noise_scheduler, optimizer, lr_scheduler, batch, noise=nz, ema=ema,
+                         snr_gamma=snr_gamma)
 
 
 def fit(config, model, noise_scheduler, optimizer, train_dataloader, lr_scheduler, sample_steps: int = 750,
-        on_step=None, overlap_noise: bool = True, noise="host", ema=None):
+        on_step=None, overlap_noise: bool = True, noise="host", ema=None, snr_gamma=None):
     """Train for ``config.num_epochs`` epochs.  `config` carries the reference's TrainingConfig fields (train.py:13-29):
     mixed_precision, gradient_accumulation_steps, output_dir, num_epochs, save_image_epochs, save_model_epochs,
     eval_batch_size, seed.  Returns the number of optimisation steps taken on this rank.  `overlap_noise=False` draws each
@@ -214,7 +231,9 @@ def fit(config, model, noise_scheduler, optimizer, train_dataloader, lr_schedule
     not the reference's values.  `ema`: an ``EMAModel`` of the model's parameters (opt-in, as in diffusers'
     train_unconditional.py): averaged after every optimizer step; the per-epoch sample and the saved pipeline then use the
     AVERAGED weights (store, copy_to, sample and save, restore), ``<output_dir>/unet_ema`` is written with
-    ``ema.save_pretrained`` at every model save, and training goes on from the raw weights, bit for bit as without it."""
+    ``ema.save_pretrained`` at every model save, and training goes on from the raw weights, bit for bit as without it.
+    `snr_gamma`: min-SNR-gamma loss weighting, see ``train_step``; the training target follows the scheduler's
+    ``prediction_type``, and the saved ``scheduler_config.json`` carries it to the sampling pipelines."""
     accelerator = Accelerator(mixed_precision=config.mixed_precision,
                               gradient_accumulation_steps=config.gradient_accumulation_steps, log_with="tensorboard",
                               project_dir=os.path.join(config.output_dir, "logs"))
@@ -230,7 +249,7 @@ def fit(config, model, noise_scheduler, optimizer, train_dataloader, lr_schedule
         noise = DeviceNoise(seed=getattr(config, "seed", 0), rank=accelerator.process_index)
     for epoch in range(config.num_epochs):
         for loss in train_steps(accelerator, model, noise_scheduler, optimizer, lr_scheduler, train_dataloader, overlap_noise,
-                                noise=noise, ema=ema):
+                                noise=noise, ema=ema, snr_gamma=snr_gamma):
             record = {"loss": loss.item(), "lr": lr_scheduler.get_last_lr()[0], "step": step}
             accelerator.log(record, step=step)
             if on_step is not None:

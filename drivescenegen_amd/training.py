@@ -44,10 +44,26 @@ class _MSEFn(torch.autograd.Function):
         return d, None
 
 
-def mse_loss(pred, target):
-    """``F.mse_loss(pred, target)`` (mean reduction, training_pipeline.py:85) on the HIP engine."""
+class _WeightedMSEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, weights):
+        loss, dpred = ops.mse_loss_weighted(pred.detach(), target.detach(), weights.detach())
+        ctx.dpred = dpred
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        d = ops.scale(ctx.dpred, gout.reshape(1).contiguous(), 1.0, out=ctx.dpred)
+        return d, None, None
+
+
+def mse_loss(pred, target, weights=None):
+    """``F.mse_loss(pred, target)`` (mean reduction, training_pipeline.py:85) on the HIP engine.  `weights` (fp32, one per
+    leading-dim sample, e.g. ``scheduler.snr_weights(gamma, device)[timesteps]``): the mean of weights[n] * (pred - target)^2."""
     if not pred.is_cuda:
         raise RuntimeError("drivescenegen_amd.mse_loss runs on the MI355X HIP engine only (got a CPU tensor)")
+    if weights is not None:
+        return _WeightedMSEFn.apply(pred, target, weights)
     return _MSEFn.apply(pred, target)
 
 

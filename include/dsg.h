@@ -359,6 +359,43 @@ int dsg_ddpm_step(const float* sample, const float* eps, const float* noise /* N
 int dsg_ddim_step(const float* sample, const float* eps, float* prev, int64_t numel,
                   float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float clip, float sqrt_alpha_prev,
                   float dir_coef, void* stream);
+/* What the network's output stands for (diffusers' `prediction_type`): the noise, the clean sample, or the velocity
+ * v = sqrt(abar)*eps - sqrt(1 - abar)*x0 (Salimans & Ho, "Progressive Distillation for Fast Sampling of Diffusion Models", 2022). */
+typedef enum { DSG_PRED_EPSILON = 0, DSG_PRED_SAMPLE = 1, DSG_PRED_V = 2 } dsg_pred_type;
+/* The DDPM / DDIM step for any dsg_pred_type.  Per element, every operation fp32 and rounded on its own, in exactly this order
+ * (tests/predtype_oracle.py restates it, tests/test_gpu_predtype.py checks it bit for bit); x the sample, m the model output,
+ * sb = sqrt_beta_prod_t, sa = sqrt_alpha_prod_t:
+ *     epsilon:  p0 = (x - sb*m) / sa                      pe = m
+ *     sample:   p0 = m                                    pe = (x - sa*m) / sb         IEEE division; sb == 0 divides by zero, as
+ *                                                                                      diffusers does at abar = 1 (inf / NaN out)
+ *     v:        p0 = sa*x - sb*m                          pe = sa*m + sb*x
+ *     p0 is clamped to +-clip when clip > 0; pe is taken from the UNCLAMPED values (use_clipped_model_output=False)
+ *     DDPM:  prev = coef_x0*p0 + coef_xt*x  (+ sigma*z when noise != NULL)
+ *     DDIM:  prev = sqrt_alpha_prev*p0 + dir_coef*pe
+ * With DSG_PRED_EPSILON the result is bitwise dsg_ddpm_step's / dsg_ddim_step's.  `noise` as in dsg_ddpm_step (device or pinned
+ * host memory, NULL when t == 0).  All pointers 16-byte aligned: dwordx4 accesses (the last numel % 4 elements singly);
+ * otherwise dword accesses.  No loop depends on the data.  Checked before any HIP call: NULL pointers, numel <= 0, a pred_type
+ * outside the enum, `prev` overlapping an input. */
+int dsg_ddpm_step_pt(const float* sample, const float* model_out, const float* noise /* NULL when t == 0 */, float* prev,
+                     int64_t numel, int32_t pred_type /* dsg_pred_type */, float sqrt_beta_prod_t, float sqrt_alpha_prod_t,
+                     float clip /* <=0: no clip */, float coef_x0, float coef_xt, float sigma, void* stream);
+int dsg_ddim_step_pt(const float* sample, const float* model_out, float* prev, int64_t numel, int32_t pred_type /* dsg_pred_type */,
+                     float sqrt_beta_prod_t, float sqrt_alpha_prod_t, float clip, float sqrt_alpha_prev, float dir_coef,
+                     void* stream);
+/* The training step's x_t and its velocity target in ONE pass over (x0, noise); per element of sample n:
+ *     noisy  = sqrt_a[n]*x0 + sqrt_1ma[n]*z          two multiplies, one add: bitwise dsg_add_noise
+ *     target = sqrt_a[n]*z  - sqrt_1ma[n]*x0         two multiplies, one subtract: diffusers' get_velocity
+ * Either output may be NULL (both NULL is an argument error).  Any per_sample: a 4-element group that straddles two samples
+ * takes each element's own coefficients.  dsg_add_noise_target_philox makes z in the kernel -- element e = element e of
+ * dsg_philox_normal(n * per_sample, seed, offset), the stream of dsg_add_noise_philox, bit for bit -- and writes `noisy` and
+ * `target` only.  Checked before any HIP call: NULL pointers, n <= 0, per_sample <= 0, an output overlapping an input or the
+ * other output. */
+int dsg_add_noise_target(const float* x0, const float* noise, const float* sqrt_a /* device [N] */,
+                         const float* sqrt_1ma /* device [N] */, float* noisy /* may be NULL */, float* target /* may be NULL */,
+                         int32_t n, int64_t per_sample, void* stream);
+int dsg_add_noise_target_philox(const float* x0, const float* sqrt_a /* device [N] */, const float* sqrt_1ma /* device [N] */,
+                                float* noisy /* may be NULL */, float* target /* may be NULL */, int32_t n, int64_t per_sample,
+                                uint64_t seed, uint64_t offset, void* stream);
 /* Dynamic thresholding (Saharia et al., "Imagen", 2022, section 2.3; diffusers 0.20.0 `thresholding=True`, `_threshold_sample`):
  * the data prediction of a step is limited per SAMPLE by a quantile of its own magnitudes instead of the static +-clip.
  * The arithmetic is pinned bit for bit (tests/dynthresh_oracle.py restates it, tests/test_gpu_dynthresh.py checks it): all
@@ -691,6 +728,12 @@ int dsg_silu_bwd(const float* z, const float* dy, int64_t numel, float* dz, void
  * ws: >= 2048 doubles. */
 int dsg_mse_loss(const float* pred, const float* target, int64_t numel, float grad_scale, float* loss, float* dpred,
                  double* ws, size_t ws_bytes, void* stream);
+/* dsg_mse_loss with one weight per sample (min-SNR-gamma loss weighting, Hang et al., 2023); pred / target are [n, per_sample]:
+ *     loss[0] = (1 / (n*per_sample)) * sum_n w[n] * sum_i (pred - target)^2        partial sums in double, fixed order
+ *     dpred   = (coef * w[n]) * (pred - target),  coef = 2*grad_scale / (float)(n*per_sample)     (skipped when NULL)
+ * With every w == 1 both are bitwise dsg_mse_loss's.  ws: >= 2048 doubles, as for dsg_mse_loss. */
+int dsg_mse_loss_weighted(const float* pred, const float* target, const float* w /* device [n] */, int32_t n, int64_t per_sample,
+                          float grad_scale, float* loss, float* dpred, double* ws, size_t ws_bytes, void* stream);
 int dsg_l2_norm(const float* x, int64_t numel, float* norm, double* ws, size_t ws_bytes, void* stream);
 int dsg_clip_scale(float* g, int64_t numel, const float* total_norm, float max_norm, void* stream);
 /* GradScaler.unscale_ (accelerate's fp16 path, training_pipeline.py:86-91 under train.py:24): g *= inv_scale in place;
