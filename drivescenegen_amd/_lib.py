@@ -249,6 +249,8 @@ SIGNATURES = {
     "dsg_png_decode_batch": [C.POINTER(C.c_char_p), _i32, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i32)],
     "dsg_hist_u8": [_vp, _i32, _i32, _i32, _vp, _vp],
     "dsg_mask_lut_u8": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, C.c_uint8, C.c_uint8, _vp, _vp],
+    "dsg_thin_lut_u8": [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp],
+    "dsg_skel_nodes_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
     "dsg_prof_enable": [_i32],
     "dsg_set_tuning": [_i32, _i32],
     "dsg_tuning_epoch": [],

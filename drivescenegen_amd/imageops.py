@@ -345,3 +345,116 @@ def agent_mask_batch(images_u8: torch.Tensor, channel: int = 2, thresh: int = 10
     lut1 = ((f * 255).astype(np.uint8) > thresh).astype(np.uint8)
     luts = np.broadcast_to(np.stack([lut1, lut1])[None], (images_u8.shape[0], 2, 256))
     return _mask_lut(images_u8, luts, channel, -1, 255, 0)
+
+
+# --------------------------------------------------------------------------------------------------
+# f2, continued: the skeleton stage (extract_network.py:270-277) -- csrc/skeleton.hip
+# --------------------------------------------------------------------------------------------------
+DEFAULT_NODE_CAP = 4096    # rows of skeleton_nodes_batch's coordinate list per image (a 512 x 512 lane skeleton has a few dozen nodes)
+
+
+def zhang_suen_lut() -> np.ndarray:
+    """uint8 [256], the default thinning table (Zhang & Suen, CACM 27(3), 1984), indexed by an on pixel's neighbour code
+    NW 1 + N 2 + NE 4 + E 8 + SE 16 + S 32 + SW 64 + W 128 (N = smaller index on axis 0, W = smaller index on axis 1).
+    Bit 0 = delete in the first sub-iteration, bit 1 = delete in the second.  A code is marked when 2 <= B <= 6 (B on
+    neighbours) and A = 1 (A off -> on steps walking N, NE, E, SE, S, SW, W, NW, N); bit 0 also needs N.E.S = 0 and E.S.W = 0,
+    bit 1 needs N.E.W = 0 and N.S.W = 0.  Parity with scikit-image's own table is unpinned (scikit-image is not a dependency):
+    ``skeletonize_batch(lut=...)`` takes any table of this layout."""
+    code = np.arange(256)
+    nw, n, ne, e, se, s, sw, w = [(code >> k) & 1 for k in range(8)]
+    walk = np.stack([n, ne, e, se, s, sw, w, nw])
+    b = walk.sum(0)
+    a = ((walk == 0) & (np.roll(walk, -1, axis=0) == 1)).sum(0)
+    marked = (b >= 2) & (b <= 6) & (a == 1)
+    first = marked & (n * e * s == 0) & (e * s * w == 0)
+    second = marked & (n * e * w == 0) & (n * s * w == 0)
+    return (first * 1 + second * 2).astype(np.uint8)
+
+
+_default_thin_lut = {}   # device -> the default table on it (uploaded once: a later call copies nothing and can be captured)
+
+
+def _thin_lut_on(device, lut):
+    if lut is None:
+        t = _default_thin_lut.get(device)
+        if t is None:
+            t = _default_thin_lut[device] = torch.from_numpy(zhang_suen_lut()).to(device)
+        return t
+    a = np.asarray(lut)
+    if a.shape != (256,) or not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() > 3:
+        raise ValueError("skeletonize_batch: lut must hold 256 integers in 0..3 (bit 0: first sub-iteration, bit 1: second)")
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(device)
+
+
+def skeletonize_batch(mask_u8: torch.Tensor, lut=None, max_iters=None, return_iters=False):
+    """``morphology.skeletonize`` of extract_network (vectorization/graph/extract_network.py:272) for a batch that is still on
+    the GPU: uint8 [N, H, W] (non-zero = on) -> uint8 [N, H, W] skeleton of 0 / 1, in ONE launch (one workgroup per image, the
+    image bit-packed in LDS, iterated to convergence there).  With ``return_iters`` also int32 [N], the iterations each image
+    took, the last idle one included.
+
+    The algorithm is the two-sub-iteration parallel thinning of Zhang & Suen (1984), driven by ``lut`` (default
+    ``zhang_suen_lut()``; any 256 values in 0..3 of that layout, checked on the host).  Parity with scikit-image's table is
+    unpinned; a user who has scikit-image can pass its table.  The reference thins ``mask.T``: with the default table the
+    result is the same (transposed) either way; with a custom table it may not be -- transpose the input to follow it.
+
+    ``max_iters`` (default H + W) bounds the loop.  An image that has not converged by then is returned as far as it got
+    and its iteration count is -1: with ``return_iters`` that raises, without it nothing is read back (the default path makes
+    no device-to-host copy).  Under stream capture (``torch.cuda.graph``): the default table is uploaded to a device on the
+    first call that uses it there, so make one call outside the capture first; a custom ``lut`` is uploaded on every call and
+    cannot be captured.  Images whose packed form exceeds one workgroup's LDS (beyond about 600 x 600: 608 x 608 fits, 640 x 640 does not) are refused."""
+    if not isinstance(mask_u8, torch.Tensor) or not mask_u8.is_cuda or mask_u8.dtype != torch.uint8 or mask_u8.dim() != 3:
+        raise RuntimeError("skeletonize_batch: expects a uint8 GPU tensor [N, H, W] (no CPU fallback)")
+    n, h, w = mask_u8.shape
+    table = _thin_lut_on(mask_u8.device, lut)
+    x = mask_u8.contiguous()
+    skel = torch.empty((n, h, w), dtype=torch.uint8, device=x.device)
+    iters = torch.empty((n,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dsg_thin_lut_u8(x.data_ptr(), n, h, w, table.data_ptr(), int(h + w if max_iters is None else max_iters),
+                                              skel.data_ptr(), iters.data_ptr(), _lib.stream_ptr(x.device)))
+    if not return_iters:
+        return skel
+    if bool((iters < 0).any().item()):
+        raise RuntimeError(f"skeletonize_batch: images {torch.nonzero(iters < 0).flatten().tolist()} had not converged after "
+                           f"{int(h + w if max_iters is None else max_iters)} iterations")
+    return skel, iters
+
+
+def skeleton_nodes_batch(skel_u8: torch.Tensor, cap=None, return_class=False):
+    """``zhang_suen_node_detection`` (vectorization/graph/extract_network.py:34-93, called at :240) for a batch on the GPU:
+    uint8 [N, H, W] (non-zero = on; any image is legal, not only a skeleton) -> (coords int32 [N, cap, 2], counts int32 [N]).
+    A node is an on pixel whose A (off -> on steps walking N, NE, E, SE, S, SW, W, NW, N, outside = off) is 1 (end point) or
+    >= 3 (branching point).  ``coords[i, :k]`` are the (axis-0 index, axis-1 index) pairs of image i in row-major order of the
+    array as given -- the reference's list order -- with k = min(counts[i], cap); the rows behind them are -1.
+    ``counts[i]`` is always the TRUE number of nodes: nothing is read back here, so the caller compares ``counts`` with
+    ``cap`` (default ``DEFAULT_NODE_CAP`` = 4096) and calls again with a larger one if a list was cut.
+    With ``return_class`` also uint8 [N, H, W]: 0 = not a node, else A."""
+    if not isinstance(skel_u8, torch.Tensor) or not skel_u8.is_cuda or skel_u8.dtype != torch.uint8 or skel_u8.dim() != 3:
+        raise RuntimeError("skeleton_nodes_batch: expects a uint8 GPU tensor [N, H, W] (no CPU fallback)")
+    n, h, w = skel_u8.shape
+    cap = DEFAULT_NODE_CAP if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError("skeleton_nodes_batch: cap must not be negative")
+    x = skel_u8.contiguous()
+    coords = torch.full((n, cap, 2), -1, dtype=torch.int32, device=x.device)
+    counts = torch.empty((n,), dtype=torch.int32, device=x.device)
+    cls = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if return_class else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dsg_skel_nodes_u8(x.data_ptr(), n, h, w, None if cls is None else cls.data_ptr(),
+                                                coords.data_ptr() if cap else None, cap, counts.data_ptr(),
+                                                _lib.stream_ptr(x.device)))
+    return (coords, counts, cls) if return_class else (coords, counts)
+
+
+def lane_skeleton_batch(images_u8: torch.Tensor):
+    """A batch of generated uint8 images [N, H, W, >=2] (GPU) -> (mask, skeleton, coords, counts): ``gray_mask_batch``, then
+    ``skeletonize_batch``, then ``skeleton_nodes_batch`` with their defaults.  Stands in for the head of the reference's lane
+    extraction: get_gray_image (vectorization/utils/image_utils.py:13-43), ``morphology.skeletonize`` and
+    ``zhang_suen_node_detection`` (vectorization/graph/extract_network.py:270-277, :272 and :240).  The reference thins and
+    scans ``mask.T``; here the arrays keep the image's own orientation (the default table gives the same skeleton either way),
+    so swap the two coordinates -- and re-sort -- to get the reference's (x, y) list.  What follows (dense nodes, find_paths)
+    is host graph code and not part of this engine."""
+    mask = gray_mask_batch(images_u8)
+    skel = skeletonize_batch(mask)
+    coords, counts = skeleton_nodes_batch(skel)
+    return mask, skel, coords, counts

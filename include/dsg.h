@@ -805,6 +805,35 @@ int dsg_mask_lut_u8(const uint8_t* img, int32_t n, int32_t hw, int32_t c, int32_
                     uint8_t on_value, uint8_t off_value, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Skeleton stage (continued): what extract_network does with the lane mask next
+ * (vectorization/graph/extract_network.py:270-277).  One workgroup per image, one launch per batch.
+ *   dsg_thin_lut_u8    `morphology.skeletonize` (:272) as table-driven two-sub-iteration parallel thinning (Zhang & Suen,
+ *                      CACM 27(3), 1984).  mask uint8 [n][h][w], non-zero = on, outside the image = off.  An on pixel's code is
+ *                      NW 1 + N 2 + NE 4 + E 8 + SE 16 + S 32 + SW 64 + W 128 (N = smaller index on axis 0, W = smaller
+ *                      index on axis 1); lut256[code] bit 0 = delete in the first sub-iteration, bit 1 = in the second
+ *                      (256 device bytes).  A sub-iteration reads the image as the previous one left it and deletes all
+ *                      marked pixels together; iterations (first, then second sub-iteration) repeat until one deletes
+ *                      nothing.  skel uint8 [n][h][w] of 0 / 1, must not alias mask; iters[i] = iterations run, the last
+ *                      idle one included, or -1 when image i had not converged after max_iters (skel then holds what it
+ *                      has thinned to: the loop is bounded whatever the table).  The bit-packed image with its zero
+ *                      border and one byte per word, (h + 2) * (ceil(w / 32) + 2) * 5 + 528 bytes, must fit 64 KiB of LDS
+ *                      (512 x 512: 45.7 KiB; 608 x 608 fits, 640 x 640 does not): DSG_ERR_INVALID_ARG before any launch
+ *                      otherwise.
+ *   dsg_skel_nodes_u8  `zhang_suen_node_detection` (:34-93, called at :240).  A(p) = off->on steps walking N, NE, E, SE, S, SW,
+ *                      W, NW, N round an on pixel (outside = off); a node has A = 1 (end point) or A >= 3 (branching
+ *                      point).  Any uint8 [n][h][w] image is legal input (non-zero = on), h * w <= 2^30.  node_class (or
+ *                      NULL) uint8 [n][h][w]: 0 = not a node, else A.  counts[i] = the true number of nodes of image i;
+ *                      coords int32 [n][cap][2] receives the first min(counts[i], cap) (axis-0 index, axis-1 index) pairs in
+ *                      row-major order -- the reference's list order -- and the rows behind them are not written
+ *                      (cap == 0: coords may be NULL).  The order is fixed by counts and a scan, not by atomics.
+ * Both are stream-asynchronous, allocate nothing and never synchronise.
+ * ---------------------------------------------------------------------------------------- */
+int dsg_thin_lut_u8(const uint8_t* mask, int32_t n, int32_t h, int32_t w, const uint8_t* lut256, int32_t max_iters,
+                    uint8_t* skel, int32_t* iters, void* stream);
+int dsg_skel_nodes_u8(const uint8_t* skel, int32_t n, int32_t h, int32_t w, uint8_t* node_class, int32_t* coords, int32_t cap,
+                      int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Direct scene rasteriser: the reference's matplotlib drawing of lane way-points / segments
  * (utils/datasets/rasterization.py:57-126) and agent rectangles (utils/datasets/visualization.py:283-296) as one
  * pass over antialiased oriented boxes in pixel space, composited in list order.
