@@ -384,7 +384,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
                                                     float* __restrict__ m, float* __restrict__ v, int64_t numel,
                                                     float lr, float beta1, float beta2, float eps, float wd,
                                                     float bc1, float bc2_sqrt, const float* __restrict__ total_norm,
-                                                    float max_norm) {
+                                                    float max_norm, float omb1, float omb2) {
   float gs = 1.f;
   if (total_norm) {
     const float cf = max_norm / (total_norm[0] + 1e-6f);
@@ -394,8 +394,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256) {
     const float gi = g[i] * gs;
     float pi = p[i] * (1.f - lr * wd);
-    const float mi = m[i] + (gi - m[i]) * (1.f - beta1);   // lerp form, as torch
-    const float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
+    // omb1 / omb2: 1 - beta formed in fp64 on the host and rounded once, as torch rounds its `value=1 - beta2` -- 1.f - (float)0.999
+    // is 1.3e-5 (relative) away from (float)0.001, and exp_avg_sq carried that factor
+    const float mi = m[i] + (gi - m[i]) * omb1;   // lerp form, as torch
+    const float vi = v[i] * beta2 + omb2 * gi * gi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     pi -= step * (mi / denom);
     p[i] = pi;
@@ -412,8 +414,8 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float* __restrict__ g, 
   for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < numel; i += (int64_t)gridDim.x * 256) g[i] *= cf;
 }
 
-// GradScaler.unscale_: g *= inv in place; *found |= any(!isfinite(g)) (checked on the scaled-back value, like torch's
-// _amp_foreach_non_finite_check_and_unscale_)
+// GradScaler.unscale_: g *= inv in place; *found |= any(!isfinite(g)), checked on the value BEFORE scaling, like torch's
+// _amp_foreach_non_finite_check_and_unscale_ (a finite value whose product with inv overflows is not flagged)
 __global__ __launch_bounds__(256) void unscale_check_kernel(float* __restrict__ g, int64_t numel, float inv,
                                                             int* __restrict__ found) {
   bool bad = false;
@@ -1149,7 +1151,7 @@ DSG_API int dsg_adamw_step(float* param, const float* grad, float* exp_avg, floa
   hipLaunchKernelGGL(dsg::adamw_kernel, dim3(dsg::stream_blocks2(numel)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), param, grad, exp_avg, exp_avg_sq, numel, (float)lr,
                      (float)beta1, (float)beta2, (float)eps, (float)weight_decay, (float)bc1, (float)sqrt(bc2),
-                     total_norm, max_norm);
+                     total_norm, max_norm, (float)(1.0 - beta1), (float)(1.0 - beta2));
   DSG_LAUNCH_CHECK();
   return DSG_OK;
 }

@@ -410,6 +410,21 @@ def gn_scale_shift_from_parts(stats0, gamma, beta, groups, eps, hw, stats1=None)
     return ss
 
 
+def gn_scale_shift_from_parts_bound(stats0, gamma, beta, groups, eps, hw, stats1=None, bound=None):
+    """dsg_gn_finalize_parts_bound: gn_scale_shift_from_parts plus the per-image range bound the same statistics give
+    (float bits in an int32 [N] tensor, maxed into `bound`: zeros when not given); returns (scale_shift, bound)."""
+    n, c0, t0 = stats0.shape[0], stats0.shape[1], stats0.shape[2]
+    c1, t1 = (stats1.shape[1], stats1.shape[2]) if stats1 is not None else (0, 0)
+    ss = torch.empty((n, c0 + c1, 2), dtype=torch.float32, device=stats0.device)
+    if bound is None:
+        bound = torch.zeros(n, dtype=torch.int32, device=stats0.device)
+    with torch.cuda.device(stats0.device):
+        _lib.check(_lib.load().dsg_gn_finalize_parts_bound(_lib.ptr(stats0), c0, t0, _lib.ptr(stats1), c1, t1,
+                                                           _lib.ptr(gamma), _lib.ptr(beta), n, groups, hw, float(eps),
+                                                           _lib.ptr(ss), _lib.ptr(bound), _st(stats0)))
+    return ss, bound
+
+
 def gn_scale_shift(src0, gamma, beta, groups, eps, src1=None):
     """Per-(n, c) scale/shift of GroupNorm over cat(src0, src1): [N][C][2]."""
     lib = _lib.load()

@@ -53,6 +53,7 @@ SUITE = {
     "test_gpu_conv_in.py": {},
     "test_gpu_conv_out.py": {},
     "test_gpu_range_guard.py": {},
+    "test_gpu_stream_edges.py": {},
     "test_gpu_train_step.py": {},   # (its two steps are checked against the fp64 oracle: check (d) of a whole step)
 }
 
