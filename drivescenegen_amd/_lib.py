@@ -251,6 +251,12 @@ SIGNATURES = {
     "dsg_mask_lut_u8": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, C.c_uint8, C.c_uint8, _vp, _vp],
     "dsg_thin_lut_u8": [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp],
     "dsg_skel_nodes_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "dsg_ccl_workspace_bytes": [_i32, _i32, _i32, C.POINTER(_sz)],
+    "dsg_ccl_tile_shape": [C.POINTER(_i32), C.POINTER(_i32)],
+    "dsg_ccl_u8": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp],
+    "dsg_cc_stats_i32": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp],
+    "dsg_cc_centers_i32": [_vp, _vp, _i32, _i32, _vp, _vp],
+    "dsg_merge_nodes_i32": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i64, _vp, _vp],
     "dsg_prof_enable": [_i32],
     "dsg_set_tuning": [_i32, _i32],
     "dsg_tuning_epoch": [],

@@ -452,9 +452,151 @@ def lane_skeleton_batch(images_u8: torch.Tensor):
     extraction: get_gray_image (vectorization/utils/image_utils.py:13-43), ``morphology.skeletonize`` and
     ``zhang_suen_node_detection`` (vectorization/graph/extract_network.py:270-277, :272 and :240).  The reference thins and
     scans ``mask.T``; here the arrays keep the image's own orientation (the default table gives the same skeleton either way),
-    so swap the two coordinates -- and re-sort -- to get the reference's (x, y) list.  What follows (dense nodes, find_paths)
-    is host graph code and not part of this engine."""
+    so swap the two coordinates -- and re-sort -- to get the reference's (x, y) list.  This is the list after extract_network.py:240;
+    ``lane_nodes_batch`` goes on to the one ``connect_graph`` works with (dense nodes merged in, :241-242).  find_paths and what
+    follows is host graph code and not part of this engine."""
     mask = gray_mask_batch(images_u8)
     skel = skeletonize_batch(mask)
     coords, counts = skeleton_nodes_batch(skel)
     return mask, skel, coords, counts
+
+
+# --------------------------------------------------------------------------------------------------
+# f2, continued: connected components (extract_network.py:96-122, :241-242; extract_vehicles.py:147-148) -- csrc/ccl.hip
+# --------------------------------------------------------------------------------------------------
+def ccl_tile_shape():
+    """(rows, columns) of the tile one workgroup of the labelling kernel holds in LDS; images larger than that are merged
+    across tile borders by a second launch."""
+    import ctypes as C
+    th, tw = C.c_int32(), C.c_int32()
+    _lib.check(_lib.load().dsg_ccl_tile_shape(C.byref(th), C.byref(tw)))
+    return th.value, tw.value
+
+
+def _need(fn, t, dtype, dim):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or t.dim() != dim:
+        raise RuntimeError(f"{fn}: expects a {str(dtype).replace('torch.', '')} GPU tensor of {dim} dimensions (no CPU fallback)")
+    return t.contiguous()
+
+
+def label_batch(mask_u8: torch.Tensor, connectivity: int = 1, erode2x2: bool = False):
+    """``scipy.ndimage.label`` for a batch on the GPU: uint8 [N, H, W] (non-zero = on) -> (labels int32 [N, H, W], counts
+    int32 [N]).  ``connectivity`` 1 = 4 neighbours (scipy's default structure), 2 = 8 (``np.ones((3, 3))``).  Labels are 0 for
+    off pixels and 1..counts[i] in scipy's numbering: components in row-major order of their first pixel.  ``erode2x2`` first
+    erodes with a 2 x 2 block anchored at the larger indices, ``binary_erosion(np.pad(a, 1), np.ones((2, 2)))[1:-1, 1:-1]``
+    (extract_network.py:98), inside the kernel's read of the mask.  H * W <= 2^30; the result is bitwise reproducible.
+    Nothing is read back."""
+    x = _need("label_batch", mask_u8, torch.uint8, 3)
+    n, h, w = x.shape
+    import ctypes as C
+    lib, need = _lib.load(), C.c_size_t()
+    _lib.check(lib.dsg_ccl_workspace_bytes(n, h, w, C.byref(need)))
+    labels = torch.empty((n, h, w), dtype=torch.int32, device=x.device)
+    counts = torch.empty((n,), dtype=torch.int32, device=x.device)
+    ws = torch.empty((need.value // 4,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.dsg_ccl_u8(x.data_ptr(), n, h, w, int(connectivity), int(bool(erode2x2)), labels.data_ptr(),
+                                  counts.data_ptr(), ws.data_ptr(), need.value, _lib.stream_ptr(x.device)))
+    return labels, counts
+
+
+def _cap_of(fn, cap):
+    cap = DEFAULT_NODE_CAP if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError(f"{fn}: cap must not be negative")
+    return cap
+
+
+def _stats_raw(fn, labels, counts, cap):
+    x, c = _need(fn, labels, torch.int32, 3), _need(fn, counts, torch.int32, 1)
+    n, h, w = x.shape
+    if c.shape[0] != n:
+        raise ValueError(f"{fn}: counts must have one entry per image")
+    raw = torch.full((n, cap, 8), 0, dtype=torch.int64, device=x.device)   # one 64-byte dsg_cc_stat per row
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().dsg_cc_stats_i32(x.data_ptr(), n, h, w, c.data_ptr(), raw.data_ptr() if cap else None, cap,
+                                               _lib.stream_ptr(x.device)))
+    return raw, c
+
+
+def component_stats_batch(labels: torch.Tensor, counts: torch.Tensor, cap=None) -> dict:
+    """Per-component statistics of ``label_batch``'s output, rows in label order (label k in row k - 1), ``cap`` rows per image
+    (default ``DEFAULT_NODE_CAP``); rows at ``min(counts[i], cap)`` and beyond are zero (area 0).  A dict of views of ONE
+    tensor ``raw`` int64 [N, cap, 8], the C struct ``dsg_cc_stat`` (include/dsg.h):
+      ``area``    int32 [N, cap]       pixels
+      ``bbox``    int32 [N, cap, 4]    r0, c0, r1, c1, half-open like ``scipy.ndimage.find_objects``
+      ``sums``    int64 [N, cap, 5]    sum of r, c, r*r, c*c, r*c over the component's pixels (r = axis-0 index)
+      ``centers`` int32 [N, cap, 2]    (sum_r // area, sum_c // area) = ``int()`` of ``center_of_mass``; -1 behind the list
+    Integer sums: exact and run-to-run identical.  Centroid and second moments follow as sums / area on the caller's side.
+    H and W <= 32768."""
+    cap = _cap_of("component_stats_batch", cap)
+    raw, c = _stats_raw("component_stats_batch", labels, counts, cap)
+    n = raw.shape[0]
+    words = raw.view(torch.int32).view(n, cap, 16)
+    centers = torch.full((n, cap, 2), -1, dtype=torch.int32, device=raw.device)
+    with torch.cuda.device(raw.device):
+        _lib.check(_lib.load().dsg_cc_centers_i32(raw.data_ptr() if cap else None, c.data_ptr(), n, cap,
+                                                 centers.data_ptr() if cap else None, _lib.stream_ptr(raw.device)))
+    return {"raw": raw, "area": words[:, :, 0], "bbox": words[:, :, 1:5], "sums": raw[:, :, 3:8], "centers": centers}
+
+
+def dense_skeleton_nodes_batch(skel_u8: torch.Tensor, cap=None):
+    """``find_dense_skeleton_nodes`` (vectorization/graph/extract_network.py:96-103) for a batch on the GPU: uint8 [N, H, W]
+    -> (coords int32 [N, cap, 2], counts int32 [N]).  The image is eroded with a 2 x 2 block, labelled with 4-connectivity and
+    each component gives the floor of its centre of mass, in label order; rows behind the list are -1, ``counts`` is the true
+    number of components (compare it with ``cap``, default ``DEFAULT_NODE_CAP``, as for ``skeleton_nodes_batch``)."""
+    x = _need("dense_skeleton_nodes_batch", skel_u8, torch.uint8, 3)
+    cap = _cap_of("dense_skeleton_nodes_batch", cap)
+    labels, counts = label_batch(x, connectivity=1, erode2x2=True)
+    return component_stats_batch(labels, counts, cap)["centers"], counts
+
+
+def merge_dense_nodes_batch(coords: torch.Tensor, counts: torch.Tensor, dense_coords: torch.Tensor, dense_counts: torch.Tensor,
+                            min_distance=5):
+    """``add_dense_nodes`` (vectorization/graph/extract_network.py:106-122) for a batch on the GPU: a dense node is kept iff no
+    node of ``coords[i, :counts[i]]`` is closer than ``min_distance`` (squared distance < min_distance ** 2, strict), whatever
+    dense nodes were kept before it.  Returns (a copy of ``coords`` with the kept nodes appended behind the originals in the
+    dense list's order, as far as its rows go; counts + kept).  If ``counts[i]`` exceeds the rows of ``coords`` that list was
+    cut already: only the listed nodes are compared and nothing is appended -- compare the returned counts with the cap."""
+    fn = "merge_dense_nodes_batch"
+    a, ca = _need(fn, coords, torch.int32, 3), _need(fn, counts, torch.int32, 1)
+    d, cd = _need(fn, dense_coords, torch.int32, 3), _need(fn, dense_counts, torch.int32, 1)
+    n = a.shape[0]
+    if a.shape[2] != 2 or d.shape[2] != 2 or d.shape[0] != n or ca.shape[0] != n or cd.shape[0] != n:
+        raise ValueError(f"{fn}: expects coords [N, cap, 2], counts [N], dense_coords [N, dense_cap, 2], dense_counts [N]")
+    min_d2 = min_distance ** 2
+    if min_d2 != int(min_d2) or min_d2 < 0:
+        raise ValueError(f"{fn}: min_distance ** 2 must be a non-negative integer (coordinates are integers)")
+    out = a.clone()
+    out_counts = torch.empty_like(ca)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.load().dsg_merge_nodes_i32(out.data_ptr() if a.shape[1] else None, ca.data_ptr(), n, a.shape[1],
+                                                  d.data_ptr() if d.shape[1] else None, cd.data_ptr(), d.shape[1], int(min_d2),
+                                                  out_counts.data_ptr(), _lib.stream_ptr(a.device)))
+    return out, out_counts
+
+
+def lane_nodes_batch(images_u8: torch.Tensor):
+    """A batch of generated uint8 images [N, H, W, >=2] (GPU) -> (mask, skeleton, coords, counts): ``lane_skeleton_batch``, then
+    ``dense_skeleton_nodes_batch`` on the skeleton and ``merge_dense_nodes_batch`` with their defaults -- the node list
+    ``connect_graph`` holds after vectorization/graph/extract_network.py:240-242.  As in ``lane_skeleton_batch`` the arrays keep
+    the image's own orientation while the reference works on ``mask.T``: the 2 x 2 block is symmetric under transposition, so
+    the SET of dense nodes is the reference's with the two coordinates swapped; only the order of the list differs (components
+    are numbered in row-major order of the array as given).  What follows (find_paths, the merge loop) is host graph code."""
+    mask, skel, coords, counts = lane_skeleton_batch(images_u8)
+    dense, dense_counts = dense_skeleton_nodes_batch(skel)
+    coords, counts = merge_dense_nodes_batch(coords, counts, dense, dense_counts)
+    return mask, skel, coords, counts
+
+
+def agent_blobs_batch(images_u8: torch.Tensor, channel: int = 2, thresh: int = 100, cap=None):
+    """The blobs of extract_agents' thresholded channel (vectorization/direct/extract_vehicles.py:136-148) for a batch of
+    generated uint8 images [N, H, W, C] (GPU): ``agent_mask_batch``, ``label_batch`` with 8-connectivity and
+    ``component_stats_batch`` -> (labels int32 [N, H, W], counts int32 [N], stats dict): area, bounding box, centre and the
+    sums behind the second moments of every blob.  What this is NOT: the reference goes on with
+    ``cv2.findContours(thresh, 1, 2)``, which also returns the contours of holes, and fits ``cv2.minAreaRect`` to each; neither
+    is computed here, and parity with OpenCV is unpinned (it is not a dependency).  The table is what a host-side rectangle
+    fit starts from; everything from ``minAreaRect`` on stays host code."""
+    mask = agent_mask_batch(images_u8, channel, thresh)
+    labels, counts = label_batch(mask, connectivity=2)
+    return labels, counts, component_stats_batch(labels, counts, cap)

@@ -844,6 +844,59 @@ int dsg_rasterize_boxes(const float* boxes, int32_t nbox, float* out, int32_t h,
                         float bg2, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Connected components (continued): the primitive behind the reference's dense skeleton nodes
+ * (vectorization/graph/extract_network.py:96-122, called at :241-242: binary_erosion, scipy.ndimage.label, center_of_mass,
+ * add_dense_nodes) and behind the blobs of the agents' mask (vectorization/direct/extract_vehicles.py:147-148).
+ * Integer arithmetic only: every result is a pure function of the input, bit for bit, run after run.  All calls are
+ * stream-asynchronous, allocate nothing, never synchronise and are legal under stream capture; every check below happens
+ * before any launch.  n <= 65535 everywhere.
+ *   dsg_ccl_u8          mask uint8 [n][h][w], non-zero = on, outside the image = off, h * w <= 2^30 (an image may span any
+ *                       number of workgroups).  connectivity 1 = 4 neighbours (scipy.ndimage.label's default), 2 = 8.
+ *                       erode2x2 = 1 first replaces the image by its erosion with a 2 x 2 block anchored at the larger indices
+ *                       -- pixel (i, j) stays on iff (i-1..i) x (j-1..j) are all on and inside the image, which is
+ *                       binary_erosion(np.pad(a, 1), np.ones((2, 2)))[1:-1, 1:-1] -- inside the one read of the mask.
+ *                       labels int32 [n][h][w]: 0 = off, else 1..K in scipy's numbering (components in row-major order of
+ *                       their first pixel); counts[i] = K.  counts[i] = -1 (labels of image i then undefined, but in 0..h*w)
+ *                       if a union-find walk exceeded its bound of h * w steps; no input is known to do that -- the bound is
+ *                       there so that no loop depends on the data for its end.  `workspace`: dsg_ccl_workspace_bytes(n, h, w)
+ *                       bytes, 4-byte aligned, contents undefined before and after.  Checked: NULL pointers, dims,
+ *                       connectivity, erode2x2, the workspace's size (DSG_ERR_WORKSPACE_TOO_SMALL) and alignment, labels /
+ *                       counts / workspace overlapping the mask or each other.
+ *   dsg_ccl_tile_shape  the tile one workgroup labels in LDS (tests derive their border cases from it).
+ *   dsg_cc_stats_i32    labels as written by dsg_ccl_u8 -> stats [n][cap] records in label order (label k at index k - 1):
+ *                       area, the bounding box r0, c0, r1, c1 (half-open, like scipy.ndimage.find_objects) and the sums of r,
+ *                       c, r*r, c*c, r*c over the component's pixels.  Records at min(counts[i], cap) and beyond are not
+ *                       written (counts[i] = -1: none).  h <= 32768 and w <= 32768: with h * w <= 2^30 pixels and coordinates
+ *                       below 2^15 no sum exceeds 2^60.  stats 8-byte aligned, must not overlap labels or counts.
+ *   dsg_cc_centers_i32  coords int32 [n][cap][2] = (sum_r / area, sum_c / area) by integer division for the same records =
+ *                       the reference's (int(x), int(y)) of center_of_mass (:102-103; the fp64 quotient of two integers this
+ *                       small cannot round across an integer).  Rows at min(counts[i], cap) and beyond are not written.
+ *   dsg_merge_nodes_i32 add_dense_nodes (:106-122).  nodes int32 [n][cap][2] holds min(counts[i], cap) original nodes per image;
+ *                       dense [n][dense_cap][2] holds min(dense_counts[i], dense_cap).  A dense node is kept iff no LISTED
+ *                       original node of its image is at squared distance < min_d2 (strict; the reference's default is 25);
+ *                       dense nodes kept earlier do not count.  Kept nodes are appended to nodes[i] behind the originals, in the
+ *                       dense list's order, while rows are left (the rest of nodes[i] is not written);
+ *                       out_counts[i] = counts[i] + kept.  counts[i] > cap: the list was cut, only the listed nodes are
+ *                       compared and nothing is appended.  Checked: NULL pointers, negative caps or min_d2, out_counts or
+ *                       nodes overlapping another argument.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dsg_cc_stat {
+  int32_t area;
+  int32_t r0, c0, r1, c1; /* rows r0 <= r < r1, columns c0 <= c < c1 */
+  int32_t reserved;       /* written as 0 */
+  int64_t sum_r, sum_c, sum_rr, sum_cc, sum_rc;
+} dsg_cc_stat;            /* 64 bytes */
+int dsg_ccl_workspace_bytes(int32_t n, int32_t h, int32_t w, size_t* bytes);
+int dsg_ccl_tile_shape(int32_t* tile_h, int32_t* tile_w);
+int dsg_ccl_u8(const uint8_t* mask, int32_t n, int32_t h, int32_t w, int32_t connectivity, int32_t erode2x2, int32_t* labels,
+               int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int dsg_cc_stats_i32(const int32_t* labels, int32_t n, int32_t h, int32_t w, const int32_t* counts, dsg_cc_stat* stats,
+                     int32_t cap, void* stream);
+int dsg_cc_centers_i32(const dsg_cc_stat* stats, const int32_t* counts, int32_t n, int32_t cap, int32_t* coords, void* stream);
+int dsg_merge_nodes_i32(int32_t* nodes, const int32_t* counts, int32_t n, int32_t cap, const int32_t* dense,
+                        const int32_t* dense_counts, int32_t dense_cap, int64_t min_d2, int32_t* out_counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Measurement plumbing (no reference counterpart): per-kernel-class HIP-event timing on the launch
  * stream, used by bench.py's roofline leg.  Classes: 0 conv3x3 stride-1, 1 conv3x3 on the nearest-x2
  * upsampled input, 2 conv3x3 stride-2, 3 conv1x1, 4 direct (VALU) conv, 5 conv weight-gradient, 6 / 7 / 8 conv3x3
